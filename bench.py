@@ -83,7 +83,15 @@ def parse_args(argv=None):
     ap.add_argument("--workload", choices=["nand", "mux", "mixed", "nand_lvl2"], default="nand",
                     help="nand = BASELINE configs[1] (the metric's config); mux = configs[3]; mixed = configs[2] op mix; "
                          "nand_lvl2 = configs[4] (N = 2048 ring, 64-bit torus)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the output ciphertexts of the last timed step to DIR/<workload>_out.npy "
+                         "(float64, at most 64 MB over all ranks): two builds run with the same arguments compare word for word")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.mode == "api":
+        ap.error("--dump-outputs needs --mode ranks: in --mode api this process never sees the ciphertexts")
+    return args
 
 
 def self_launch(args):
@@ -237,6 +245,24 @@ def oracle_check(ol, L, ek, ops, in0, in1, in2, gpu_out, idx):
     c = np.ascontiguousarray(in2[idx])
     L.orc_gate_batch(ek, ops_arr, 1, 0, idx.size, out, a, b.ctypes.data, c.ctypes.data, min(L.orc_max_threads(), 32))
     return bool(np.array_equal(out.reshape(idx.size, -1), gpu_out[idx]))
+
+
+DUMP_BUDGET_BYTES = 64 * 10**6           # --dump-outputs: every file of every rank together
+
+
+def dump_outputs(out_dir, workload, words):
+    """--dump-outputs: what the timed path hands its caller in its last step -- this rank's output ciphertexts, one row of
+    n + 1 torus words per gate -- as DIR/<workload>_out[_rank<r>].npy in float64 (every uint32 word exactly).  Rows beyond
+    this rank's share of the budget are cut to a fixed seeded sample whose gate indices go to <name>_rows.npy, so that two
+    builds run with the same arguments still compare row for row."""
+    name = workload + "_out" + ("_rank%d" % RANK if WORLD > 1 else "")
+    keep = max(1, (DUMP_BUDGET_BYTES // WORLD - 4096) // (8 * words.shape[1] + 8))
+    os.makedirs(out_dir, exist_ok=True)
+    if words.shape[0] > keep:
+        rows = np.sort(np.random.default_rng(1).choice(words.shape[0], keep, replace=False))
+        words = words[rows]
+        np.save(os.path.join(out_dir, name + "_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, name + ".npy"), words.astype(np.float64))
 
 
 def cgroup_cpu_quota():
@@ -561,6 +587,8 @@ def main():
     wl = args.workload
     elapsed = distutil.max_over_ranks(timed(wl, args.steps, args.warmup), dist)
     own_s = own["s"]
+    if args.dump_outputs:                    # before anything else launches into dout
+        dump_outputs(args.dump_outputs, wl, dout.download().reshape(max(count, 1), ol.n + 1)[:count])
     br_ms, ks_ms = kernel_times(wl)
     clock_hz = clock_during("lvl2" if wl == "nand_lvl2" else "batch", lambda: run_step(wl), br_ms)      # shader clock under the workload's own launch
     # every rank's own rate, device and launch times, gathered on all ranks (gloo): rank 0 prints them

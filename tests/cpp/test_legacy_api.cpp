@@ -5,6 +5,9 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <string>
+
+#include <unistd.h>
 
 #define CUFHE_AMD_INSECURE_TEST_KEYS      // reproducible keys: this is a test
 #include "../../include/cufhe_amd_legacy.hpp"
@@ -45,10 +48,15 @@ int main(int argc, char** argv)
     }
     std::printf("encrypt/decrypt: %s\n", correct ? "PASS" : "FAIL");
 
-    // key files
+    // key files, in a directory of this run's own (runs by other users or at the same time do not collide)
     {
-        const char* f1 = "/tmp/cufhe_amd_pri.key";
-        const char* f2 = "/tmp/cufhe_amd_pub.key";
+        const char* tmp = std::getenv("TMPDIR");
+        std::string dir = std::string(tmp && *tmp ? tmp : "/tmp") + "/cufhe_amd_keys_XXXXXX";
+        if (!mkdtemp(&dir[0])) {
+            std::perror("mkdtemp");
+            return 1;
+        }
+        const std::string f1 = dir + "/pri.key", f2 = dir + "/pub.key";
         WritePriKeyToFile(pri_key, f1);
         WritePubKeyToFile(pub_key, f2);
         PriKey p2;
@@ -58,8 +66,9 @@ int main(int argc, char** argv)
         const bool same = p2.lvl0_key == pri_key.lvl0_key && p2.lvl1_key == pri_key.lvl1_key && q2.bk == pub_key.bk && q2.ksk == pub_key.ksk;
         std::printf("key files: %s\n", same ? "PASS" : "FAIL");
         correct = correct && same;
-        std::remove(f1);
-        std::remove(f2);
+        std::remove(f1.c_str());
+        std::remove(f2.c_str());
+        rmdir(dir.c_str());
     }
     if (cpu_only) {
         std::printf("%s\n", correct ? "ALL PASS" : "FAILED");
