@@ -14,6 +14,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <tuple>
 #include <unordered_map>
 #include <vector>
 
@@ -537,34 +538,45 @@ int upload_descs(DeviceState& s, Scratch& sc, const std::vector<Desc>& h, Desc**
     return 0;
 }
 
-// HIP events around a launch sequence on its own stream (cufhe_amd_profile_enable): begin before, end after
-int prof_begin(DeviceState& s, hipStream_t st, EventPair& ev)
-{
-    if (!s.profiling) return 0;
-    HIP_TRY(hipEventCreate(&ev.a));
-    HIP_TRY(hipEventCreate(&ev.b));
-    HIP_TRY(hipEventRecord(ev.a, st));
-    return 0;
-}
-int prof_end(DeviceState& s, hipStream_t st, EventPair& ev, size_t units, bool keyswitch)
-{
-    if (!s.profiling || !ev.a) return 0;
-    HIP_TRY(hipEventRecord(ev.b, st));
-    ev.units = units;
-    std::lock_guard<std::mutex> lk(s.staging_mu);
-    (keyswitch ? s.ks_events : s.br_events).push_back(ev);
-    return 0;
-}
+// HIP events around one launcher call on its stream (cufhe_amd_profile_enable): begin() creates the pair and records the first,
+// commit() records the second and hands the pair with `units` to br_events / ks_events (cufhe_amd_profile_get).  A return in
+// between destroys the pair instead of leaking it.
+struct ProfScope {
+    DeviceState& s;
+    hipStream_t st;
+    uint64_t units;
+    bool keyswitch;
+    EventPair ev{};
+    int begin()
+    {
+        if (!s.profiling) return 0;
+        HIP_TRY(hipEventCreate(&ev.a));
+        HIP_TRY(hipEventCreate(&ev.b));
+        HIP_TRY(hipEventRecord(ev.a, st));
+        return 0;
+    }
+    int commit()
+    {
+        if (!ev.a) return 0;
+        HIP_TRY(hipEventRecord(ev.b, st));
+        ev.units = units;
+        std::lock_guard<std::mutex> lk(s.staging_mu);
+        (keyswitch ? s.ks_events : s.br_events).push_back(ev);
+        ev = EventPair{};
+        return 0;
+    }
+    ~ProfScope()
+    {
+        if (ev.a) (void)hipEventDestroy(ev.a);
+        if (ev.b) (void)hipEventDestroy(ev.b);
+    }
+};
 
 int launch_blind_rotate(DeviceState& s, hipStream_t st, const LinDesc* d, size_t count, int steps, uint32_t* acc_dump)
 {
     if (count == 0) return 0;
-    EventPair ev{};
-    if (s.profiling) {
-        HIP_TRY(hipEventCreate(&ev.a));
-        HIP_TRY(hipEventCreate(&ev.b));
-        HIP_TRY(hipEventRecord(ev.a, st));
-    }
+    ProfScope prof{s, st, count, false};
+    if (int rc = prof.begin()) return rc;
     if (!s.br_lds_opt_in) {      // > 64 KiB of dynamic LDS needs an opt-in, per device
         HIP_TRY(hipFuncSetAttribute((const void*)blind_rotate_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kBrLdsBytes));
         HIP_TRY(hipFuncSetAttribute((const void*)blind_rotate_ll_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kLlLdsBytes));
@@ -638,13 +650,7 @@ int launch_blind_rotate(DeviceState& s, hipStream_t st, const LinDesc* d, size_t
         else if (g_br_shape == 2) launch_ll2(d, count, acc_dump);
         else launch_ll(d, count, acc_dump);
         HIP_TRY(hipGetLastError());
-        if (s.profiling) {
-            HIP_TRY(hipEventRecord(ev.b, st));
-            ev.units = count;
-            std::lock_guard<std::mutex> lk(s.staging_mu);
-            s.br_events.push_back(ev);
-        }
-        return 0;
+        return prof.commit();
     }
     const size_t tail = count % kRound;
     const long tail_max = std::max(auto_half ? (long)(4 * cu) : g_half_threshold, auto_ll ? (long)((g_ll2_threshold < 0 ? 6 : 5) * cu) : g_ll_threshold);
@@ -656,13 +662,7 @@ int launch_blind_rotate(DeviceState& s, hipStream_t st, const LinDesc* d, size_t
         launch_small(d, count, acc_dump);
     }
     HIP_TRY(hipGetLastError());
-    if (s.profiling) {
-        HIP_TRY(hipEventRecord(ev.b, st));
-        ev.units = count;
-        std::lock_guard<std::mutex> lk(s.staging_mu);
-        s.br_events.push_back(ev);
-    }
-    return 0;
+    return prof.commit();
 }
 // keyswitch_kernel<S> over `ksk_padded` ([kn][t][2][row_pad] u32); *opted_in: the instantiation's dynamic-LDS opt-in on this device
 template <class S>
@@ -682,12 +682,8 @@ int launch_keyswitch_shared(DeviceState& s, hipStream_t st, const typename S::De
 int launch_keyswitch(DeviceState& s, hipStream_t st, const LinDesc* d, size_t count)
 {
     if (count == 0) return 0;
-    EventPair ev{};
-    if (s.profiling) {
-        HIP_TRY(hipEventCreate(&ev.a));
-        HIP_TRY(hipEventCreate(&ev.b));
-        HIP_TRY(hipEventRecord(ev.a, st));
-    }
+    ProfScope prof{s, st, count, true};
+    if (int rc = prof.begin()) return rc;
     const long split_max = g_ks_split_threshold < 0 ? ks_auto_split(cus_of(s)) : g_ks_split_threshold;
     const long wg_max = g_ks_wg_threshold < 0 ? ks_auto_wg(cus_of(s)) : g_ks_wg_threshold;
     if ((long)count <= split_max) {
@@ -699,13 +695,7 @@ int launch_keyswitch(DeviceState& s, hipStream_t st, const LinDesc* d, size_t co
         if (int rc = launch_keyswitch_shared<KsShapeDefault>(s, st, d, count, s.ksk, &s.ks_lds_opt_in)) return rc;
     }
     HIP_TRY(hipGetLastError());
-    if (s.profiling) {
-        HIP_TRY(hipEventRecord(ev.b, st));
-        ev.units = count;
-        std::lock_guard<std::mutex> lk(s.staging_mu);
-        s.ks_events.push_back(ev);
-    }
-    return 0;
+    return prof.commit();
 }
 int launch_lincomb(hipStream_t st, const LinDesc* d, size_t count, int words)
 {
@@ -730,30 +720,38 @@ template <class GetGate>
 int run_gates_ps(int set, int device, void* stream, int level, size_t count, GetGate get);   // paramsets.inc.h
 int ps_ctxt_words(int set, int level);
 void lvl2_release_host_key();          // lvl2.inc.h
+// The compiled parameter sets of kernels_ps.hip.h in the order of their indices ("param_set", cufhe_amd_ps_*): ps_dispatch
+// (paramsets.inc.h) and the TRGSW slot size below are both taken from this one list.
+using CompiledSets = std::tuple<PsDefault, PsK2N512, PsCggi16, PsSmallMod>;
+static_assert(std::tuple_size_v<CompiledSets> == kParamSets, "every compiled parameter set is listed once");
 // a TRGSW holder's device slot (ciphertext handle of level 3) fits the NTT-domain TRGSW of every compiled set, key limbs included
-template <class PS> constexpr int kTrgswNttWordsOf = (int)(2 * PsDims<PS>::bk_ntt_step_doubles);
-constexpr int kMaxTrgswNttWords = std::max({(int)(2 * kBkStepDoubles), kTrgswNttWordsOf<PsDefault>, kTrgswNttWordsOf<PsK2N512>, kTrgswNttWordsOf<PsCggi16>});
+constexpr int kMaxTrgswNttWords =
+    std::apply([](auto... ps) { return std::max({(int)(2 * kBkStepDoubles), (int)(2 * PsDims<decltype(ps)>::bk_ntt_step_doubles)...}); }, CompiledSets{});
 int run_trlwe_ops_ps(int set, int device, void* stream, const GateRef* g, size_t n);         // paramsets.inc.h
 int ps_trgsw_to_ntt_host(int set, int device, void* stream, const uint32_t* trgsw_host, double* trgsw_ntt_host);
 // >= 0: the per-gate API (both ciphertext levels, both gate orders) runs on this compiled parameter set -- the reference's build-time
 // choice (CMakeLists.txt:8-24) serves every entry point the same way; ciphertexts then have the set's sizes (cufhe_amd_ctxt_words)
 long g_param_set = -1;
 
-template <class GetGate>
-int run_gates(int device, void* stream, int level, size_t count, GetGate get)
+// The gate lowering of every bootstrapping path (BasePath below, PsPath<PS> in paramsets.inc.h, Lvl2Path in lvl2.inc.h): a list of
+// gates -> rotation, key-switch and lincomb descriptors and one launch of each.  The path P gives
+//   RotD, KsD          the descriptors its rotation and key-switch launchers take
+//   Mid, mid_words     word type and size of the ciphertext between rotation and key switch (lvl1; lvl2 on the N = 2048 path)
+//   lvl0_words, n      lvl0 ciphertext words, CMux steps of a blind rotation
+//   ks_mu              the mu of the Mux sum in the key switch
+//   lvl1_gates         whether it has gates on Mid ciphertexts (level 1)
+//   s, ready(), rotate(), keyswitch()   its device, the readiness check and the two launchers
+// Level 0: blind rotate -> key switch (__HomGate__ br -> iks); level 1: key switch -> blind rotate (iks -> br); Not / Copy and the
+// level-1 Mux sums run last, as one lincomb.
+template <class P, class GetGate>
+int lower_gates(const P& p, hipStream_t st, int level, size_t count, GetGate get)
 {
-    if (level == 0 && g_lvl0_ring == 2048) return run_gates_lvl2(device, stream, count, get);
-    if ((level == 0 || level == 1) && g_param_set >= 0) return run_gates_ps((int)g_param_set, device, stream, level, count, get);
-    if (int rc = use_device(device)) return rc;
-    DeviceState& s = g_dev[device];
-    if (!s.keys_ready) return fail(-3, "Initialize(ek) has not been called for this device");
+    using Mid = typename P::Mid;
+    if (int rc = p.ready()) return rc;
     if (level != 0 && level != 1) return fail(-1, "level must be 0 or 1");
     if (count == 0) return 0;
-    hipStream_t st = (hipStream_t)stream;
     const uint32_t negmu = 0u - kMu;
 
-    std::vector<LinDesc> rot, ks, lin;
-    rot.reserve(count * 2); ks.reserve(count * 2); lin.reserve(count);
     // first pass: count temporaries
     size_t nrot = 0;
     for (size_t g = 0; g < count; g++) {
@@ -764,16 +762,21 @@ int run_gates(int device, void* stream, int level, size_t count, GetGate get)
     }
     Scratch sc;
     {
-        const size_t need = nrot * (kLvl1Words + kLvl0Words) * sizeof(uint32_t) +
-                            (count * 5 + 8) * sizeof(LinDesc) + 4096;
-        if (int rc = open_scratch(s, st, need, &sc)) return rc;
+        const size_t desc = std::max({sizeof(typename P::RotD), sizeof(typename P::KsD), sizeof(LinDesc)});
+        const size_t need = nrot * (P::mid_words * sizeof(Mid) + P::lvl0_words * sizeof(uint32_t)) + (count * 5 + 8) * desc + 8192;
+        if (int rc = open_scratch(p.s, st, need, &sc)) return rc;
     }
-    uint32_t *tmp1 = nullptr, *tmp0 = nullptr;   // lvl1 / lvl0 temporaries, one per rotation
+    Mid* tmp1 = nullptr;          // the rotations' results, one per rotation
+    uint32_t* tmp0 = nullptr;     // level 1: the key switches' results, one per rotation
     if (nrot) {
-        if (int rc = sc.alloc((void**)&tmp1, nrot * kLvl1Words * sizeof(uint32_t))) return rc;
+        if (int rc = sc.alloc((void**)&tmp1, nrot * P::mid_words * sizeof(Mid))) return rc;
         if (level == 1)
-            if (int rc = sc.alloc((void**)&tmp0, nrot * kLvl0Words * sizeof(uint32_t))) return rc;
+            if (int rc = sc.alloc((void**)&tmp0, nrot * P::lvl0_words * sizeof(uint32_t))) return rc;
     }
+    std::vector<typename P::RotD> rot;
+    std::vector<typename P::KsD> ks;
+    std::vector<LinDesc> lin;
+    rot.reserve(count * 2); ks.reserve(count * 2); lin.reserve(count);
     size_t ir = 0;
     for (size_t g = 0; g < count; g++) {
         const GateRef gr = get(g);
@@ -785,69 +788,70 @@ int run_gates(int device, void* stream, int level, size_t count, GetGate get)
         if (!gr.in1) return fail(-1, "gate needs a second operand");
         if (gr.op == CUFHE_AMD_MUX || gr.op == CUFHE_AMD_NMUX) {
             if (!gr.in2) return fail(-1, "mux needs a third operand");
-            uint32_t* t1a = tmp1 + (ir + 0) * kLvl1Words;
-            uint32_t* t1b = tmp1 + (ir + 1) * kLvl1Words;
+            Mid* ta = tmp1 + (ir + 0) * P::mid_words;
+            Mid* tb = tmp1 + (ir + 1) * P::mid_words;
             const bool neg = gr.op == CUFHE_AMD_NMUX;
             if (level == 0) {   // src/bootstrap_gpu.cu:515-588
-                rot.push_back({gr.in0, gr.in1, t1a, 1, 1, negmu, 0u});
-                rot.push_back({gr.in0, gr.in2, t1b, -1, 1, negmu, 0u});
-                ks.push_back({t1a, t1b, gr.out, neg ? -1 : 1, neg ? -1 : 1, neg ? negmu : kMu, 0u});
-            } else {            // src/bootstrap_gpu.cu:706-780
-                uint32_t* t0a = tmp0 + (ir + 0) * kLvl0Words;
-                uint32_t* t0b = tmp0 + (ir + 1) * kLvl0Words;
-                ks.push_back({gr.in0, gr.in1, t0a, 1, 1, negmu, 0u});
-                ks.push_back({gr.in0, gr.in2, t0b, -1, 1, negmu, 0u});
-                rot.push_back({t0a, t0a, t1a, 1, 0, 0u, 0u});
-                rot.push_back({t0b, t0b, t1b, 1, 0, 0u, 0u});
-                lin.push_back({t1a, t1b, gr.out, neg ? -1 : 1, neg ? -1 : 1, neg ? negmu : kMu, 0u});
+                rot.push_back({gr.in0, gr.in1, ta, 1, 1, negmu});
+                rot.push_back({gr.in0, gr.in2, tb, -1, 1, negmu});
+                ks.push_back({ta, tb, gr.out, neg ? -1 : 1, neg ? -1 : 1, neg ? 0u - P::ks_mu : P::ks_mu});
+            } else if constexpr (P::lvl1_gates) {   // src/bootstrap_gpu.cu:706-780: two key switches, two rotations, the sum of the extracted ciphertexts
+                uint32_t* t0a = tmp0 + (ir + 0) * P::lvl0_words;
+                uint32_t* t0b = tmp0 + (ir + 1) * P::lvl0_words;
+                ks.push_back({gr.in0, gr.in1, t0a, 1, 1, negmu});
+                ks.push_back({gr.in0, gr.in2, t0b, -1, 1, negmu});
+                rot.push_back({t0a, t0a, ta, 1, 0, 0u});
+                rot.push_back({t0b, t0b, tb, 1, 0, 0u});
+                lin.push_back({ta, tb, gr.out, neg ? -1 : 1, neg ? -1 : 1, neg ? negmu : kMu, 0u});
             }
             ir += 2;
             continue;
         }
         const int ca = kGateTab[gr.op][0], cb = kGateTab[gr.op][1];
         const uint32_t off = (uint32_t)kGateTab[gr.op][2] * kMu;
-        if (level == 0) {       // __HomGate__ br->iks, src/bootstrap_gpu.cu:402-421
-            uint32_t* t1 = tmp1 + ir * kLvl1Words;
-            rot.push_back({gr.in0, gr.in1, t1, ca, cb, off, 0u});
-            ks.push_back({t1, t1, gr.out, 1, 0, 0u, 0u});
-        } else {                // __HomGate__ iks->br, src/bootstrap_gpu.cu:383-400
-            uint32_t* t0 = tmp0 + ir * kLvl0Words;
-            ks.push_back({gr.in0, gr.in1, t0, ca, cb, off, 0u});
-            rot.push_back({t0, t0, gr.out, 1, 0, 0u, 0u});
+        if (level == 0) {       // __HomGate__ br -> iks, src/bootstrap_gpu.cu:402-421
+            Mid* t1 = tmp1 + ir * P::mid_words;
+            rot.push_back({gr.in0, gr.in1, t1, ca, cb, off});
+            ks.push_back({t1, t1, gr.out, 1, 0, 0u});
+        } else if constexpr (P::lvl1_gates) {   // __HomGate__ iks -> br, src/bootstrap_gpu.cu:383-400
+            uint32_t* t0 = tmp0 + ir * P::lvl0_words;
+            ks.push_back({gr.in0, gr.in1, t0, ca, cb, off});
+            rot.push_back({t0, t0, gr.out, 1, 0, 0u});
         }
         ir += 1;
     }
     // Mux/NMux at level 1 write their rotations to temporaries, two-input gates at level 1
     // write straight to `out`; a lincomb that reads tmp1 must run after the rotations.
-    LinDesc *drot, *dks, *dlin;
-    if (int rc = upload_descs(s, sc, rot, &drot)) return rc;
-    if (int rc = upload_descs(s, sc, ks, &dks)) return rc;
-    if (int rc = upload_descs(s, sc, lin, &dlin)) return rc;
-    const int words = level ? kLvl1Words : kLvl0Words;
+    typename P::RotD* drot;
+    typename P::KsD* dks;
+    LinDesc* dlin;
+    if (int rc = upload_descs(p.s, sc, rot, &drot)) return rc;
+    if (int rc = upload_descs(p.s, sc, ks, &dks)) return rc;
+    if (int rc = upload_descs(p.s, sc, lin, &dlin)) return rc;
     if (level == 0) {
-        if (int rc = launch_blind_rotate(s, st, drot, rot.size(), kLvl0N, nullptr)) return rc;
-        if (int rc = launch_keyswitch(s, st, dks, ks.size())) return rc;
+        if (int rc = p.rotate(st, drot, rot.size(), P::n, nullptr)) return rc;
+        if (int rc = p.keyswitch(st, dks, ks.size())) return rc;
     } else {
-        if (int rc = launch_keyswitch(s, st, dks, ks.size())) return rc;
-        if (int rc = launch_blind_rotate(s, st, drot, rot.size(), kLvl0N, nullptr)) return rc;
+        if (int rc = p.keyswitch(st, dks, ks.size())) return rc;
+        if (int rc = p.rotate(st, drot, rot.size(), P::n, nullptr)) return rc;
     }
-    if (int rc = launch_lincomb(st, dlin, lin.size(), words)) return rc;
-    return 0;
+    return launch_lincomb(st, dlin, lin.size(), level ? P::mid_words : P::lvl0_words);
 }
 
-// TRLWE-level operations recorded through the scheduler (include/cufhe_gpu.cuh:124-146,209-216,282-285;
-// src/cufhe_gates_gpu.cu:86-146): any mix of
+// The TRLWE-level operations recorded through the scheduler (include/cufhe_gpu.cuh:124-146,209-216,282-285;
+// src/cufhe_gates_gpu.cu:86-146) on BasePath or a PsPath<PS>: any mix of
 //   CUFHE_AMD_TL_BOOTSTRAP  lvl0 TLWE -> TRLWE     __BlindRotateGlobal__, src/bootstrap_gpu.cu:317-323
 //   CUFHE_AMD_TL_REFRESH    TRLWE -> TRLWE         __SEIandBootstrap2TRLWE__, :325-364
 //   CUFHE_AMD_TL_SEIKS      TRLWE -> lvl0 TLWE     __SEIandKS__, src/keyswitch_gpu.cu:26-40
-// as ONE launch sequence: sample extracts, one key-switch launch, one blind-rotate launch, scatter.
-int run_trlwe_ops(int device, void* stream, const GateRef* g, size_t n)
+// as ONE launch sequence: sample extracts, one key-switch launch, one blind-rotate launch, scatter; and the CMUXNTT calls of the level
+// (src/bootstrap_gpu.cu:197-285).  Beside what lower_gates uses the path gives se_kernel (the sample extract), trlwe_words, and
+// has_cmux with cmux(): only the small-modulus build of the reference leaves CMUXNTT out (src/cufhe_gates_gpu.cu:68-86).
+template <class P>
+int lower_trlwe_ops(const P& p, hipStream_t st, const GateRef* g, size_t n)
 {
-    if (g_param_set >= 0) return run_trlwe_ops_ps((int)g_param_set, device, stream, g, n);
-    if (int rc = use_device(device)) return rc;
-    DeviceState& s = g_dev[device];
+    DeviceState& s = p.s;
     if (n == 0) return 0;
-    hipStream_t st = (hipStream_t)stream;
+    constexpr size_t tw = P::trlwe_words;
     size_t n_se = 0, n_rot = 0, n_t0 = 0, n_cmux = 0;
     for (size_t i = 0; i < n; i++) {
         if (!g[i].out || !g[i].in0) return fail(-1, "null operand");
@@ -856,34 +860,36 @@ int run_trlwe_ops(int device, void* stream, const GateRef* g, size_t n)
             case CUFHE_AMD_TL_REFRESH: n_se++; n_rot++; n_t0++; break;
             case CUFHE_AMD_TL_SEIKS: n_se++; break;
             case CUFHE_AMD_TL_CMUX:
+                if (!P::has_cmux) return fail(-1, "CMUXNTT: the small-modulus build of the reference has none (src/cufhe_gates_gpu.cu:68-86)");
                 if (!g[i].in1 || !g[i].in2) return fail(-1, "CMUXNTT: null operand");
                 n_cmux++;
                 break;
             default: return fail(-1, "unknown TRLWE-level op");
         }
     }
-    if (n_cmux < n && !s.keys_ready) return fail(-3, "Initialize(ek) has not been called for this device");
+    if (n_cmux < n)
+        if (int rc = p.ready()) return rc;
     if (n_cmux && !s.ntt_ready) return fail(-3, "Initialize() has not been called for this device");
     Scratch sc;
-    const size_t need = n_se * kLvl1Words * 4 + n_t0 * kLvl0Words * 4 + n_rot * 2 * kN * 4 + (3 * n + 8) * sizeof(LinDesc) +
+    const size_t need = (n_se * P::mid_words + n_t0 * P::lvl0_words + n_rot * tw) * 4 + (3 * n + 8) * sizeof(LinDesc) +
                         n_cmux * sizeof(CmuxDesc) + 16384;
     if (int rc = open_scratch(s, st, need, &sc)) return rc;
-    if (n_cmux) {      // the CMUXNTT calls of this level: independent of the other operations of the level (the scheduler's contract)
-        std::vector<CmuxDesc> cm;
-        cm.reserve(n_cmux);
-        for (size_t i = 0; i < n; i++)
-            if (g[i].op == CUFHE_AMD_TL_CMUX) cm.push_back({g[i].in0, g[i].in1, g[i].out, (const double*)g[i].in2});
-        CmuxDesc* dcm;
-        if (int rc = upload_descs(s, sc, cm, &dcm)) return rc;
-        const unsigned blocks = (unsigned)((cm.size() + kNttWavesPerBlock - 1) / kNttWavesPerBlock);
-        hipLaunchKernelGGL(cmux_desc_kernel, dim3(blocks), dim3(kNttThreads), kNttLdsBytes, st, dcm, (int)cm.size(), s.tables);
-        HIP_TRY(hipGetLastError());
+    if (n_cmux) {      // the CMUXNTT calls of this level: independent of its other operations (the scheduler's contract); needs no key
+        if constexpr (P::has_cmux) {
+            std::vector<CmuxDesc> cm;
+            cm.reserve(n_cmux);
+            for (size_t i = 0; i < n; i++)
+                if (g[i].op == CUFHE_AMD_TL_CMUX) cm.push_back({g[i].in0, g[i].in1, g[i].out, (const double*)g[i].in2});
+            CmuxDesc* dcm;
+            if (int rc = upload_descs(s, sc, cm, &dcm)) return rc;
+            if (int rc = p.cmux(st, dcm, cm.size())) return rc;
+        }
         if (n_cmux == n) return 0;
     }
     uint32_t *t1 = nullptr, *t0 = nullptr, *dump = nullptr;
-    if (n_se) if (int rc = sc.alloc((void**)&t1, n_se * kLvl1Words * 4)) return rc;
-    if (n_t0) if (int rc = sc.alloc((void**)&t0, n_t0 * kLvl0Words * 4)) return rc;
-    if (n_rot) if (int rc = sc.alloc((void**)&dump, n_rot * 2 * kN * 4)) return rc;
+    if (n_se) if (int rc = sc.alloc((void**)&t1, n_se * P::mid_words * 4)) return rc;
+    if (n_t0) if (int rc = sc.alloc((void**)&t0, n_t0 * P::lvl0_words * 4)) return rc;
+    if (n_rot) if (int rc = sc.alloc((void**)&dump, n_rot * tw * 4)) return rc;
     std::vector<LinDesc> se, ks, rot, scat;
     size_t i_se = 0, i_t0 = 0, i_rot = 0;
     for (size_t i = 0; i < n; i++) {
@@ -891,17 +897,17 @@ int run_trlwe_ops(int device, void* stream, const GateRef* g, size_t n)
         if (g[i].op == CUFHE_AMD_TL_BOOTSTRAP) {
             rot.push_back({g[i].in0, g[i].in0, nullptr, 1, 0, 0u, 0u});
         } else {
-            uint32_t* a = t1 + i_se++ * kLvl1Words;
+            uint32_t* a = t1 + i_se++ * P::mid_words;
             se.push_back({g[i].in0, g[i].in0, a, 1, 0, 0u, 0u});
             if (g[i].op == CUFHE_AMD_TL_SEIKS) {
                 ks.push_back({a, a, g[i].out, 1, 0, 0u, 0u});
                 continue;
             }
-            uint32_t* b = t0 + i_t0++ * kLvl0Words;
+            uint32_t* b = t0 + i_t0++ * P::lvl0_words;
             ks.push_back({a, a, b, 1, 0, 0u, 0u});
             rot.push_back({b, b, nullptr, 1, 0, 0u, 0u});
         }
-        uint32_t* d = dump + i_rot++ * 2 * kN;
+        uint32_t* d = dump + i_rot++ * tw;
         scat.push_back({d, d, g[i].out, 1, 0, 0u, 0u});
     }
     LinDesc *dse, *dks, *drot, *dscat;
@@ -910,12 +916,100 @@ int run_trlwe_ops(int device, void* stream, const GateRef* g, size_t n)
     if (int rc = upload_descs(s, sc, rot, &drot)) return rc;
     if (int rc = upload_descs(s, sc, scat, &dscat)) return rc;
     if (!se.empty()) {
-        hipLaunchKernelGGL(sample_extract_desc_kernel, dim3((unsigned)(se.size() < 2048 ? se.size() : 2048)), dim3(256), 0, st, dse, (int)se.size());
+        hipLaunchKernelGGL(P::se_kernel, dim3((unsigned)(se.size() < 2048 ? se.size() : 2048)), dim3(256), 0, st, dse, (int)se.size());
         HIP_TRY(hipGetLastError());
     }
-    if (int rc = launch_keyswitch(s, st, dks, ks.size())) return rc;
-    if (int rc = launch_blind_rotate(s, st, drot, rot.size(), kLvl0N, dump)) return rc;
-    return launch_lincomb(st, dscat, scat.size(), 2 * kN);
+    if (int rc = p.keyswitch(st, dks, ks.size())) return rc;
+    if (int rc = p.rotate(st, drot, rot.size(), P::n, dump)) return rc;
+    return launch_lincomb(st, dscat, scat.size(), (int)tw);
+}
+
+// The hand-scheduled kernels (the default path)
+struct BasePath {
+    using RotD = LinDesc;
+    using KsD = LinDesc;
+    using Mid = uint32_t;
+    static constexpr int lvl0_words = kLvl0Words, mid_words = kLvl1Words, n = kLvl0N;
+    static constexpr uint32_t ks_mu = kMu;
+    static constexpr bool lvl1_gates = true, has_cmux = true;
+    static constexpr size_t trlwe_words = 2 * kN;
+    static constexpr auto se_kernel = sample_extract_desc_kernel;
+    DeviceState& s;
+    int ready() const { return s.keys_ready ? 0 : fail(-3, "Initialize(ek) has not been called for this device"); }
+    int rotate(hipStream_t st, const LinDesc* d, size_t count, int steps, uint32_t* dump) const { return launch_blind_rotate(s, st, d, count, steps, dump); }
+    int keyswitch(hipStream_t st, const LinDesc* d, size_t count) const { return launch_keyswitch(s, st, d, count); }
+    int cmux(hipStream_t st, const CmuxDesc* d, size_t count) const
+    {
+        const unsigned blocks = (unsigned)((count + kNttWavesPerBlock - 1) / kNttWavesPerBlock);
+        hipLaunchKernelGGL(cmux_desc_kernel, dim3(blocks), dim3(kNttThreads), kNttLdsBytes, st, d, (int)count, s.tables);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    }
+};
+
+template <class GetGate>
+int run_gates(int device, void* stream, int level, size_t count, GetGate get)
+{
+    if (level == 0 && g_lvl0_ring == 2048) return run_gates_lvl2(device, stream, count, get);
+    if ((level == 0 || level == 1) && g_param_set >= 0) return run_gates_ps((int)g_param_set, device, stream, level, count, get);
+    if (int rc = use_device(device)) return rc;
+    return lower_gates(BasePath{g_dev[device]}, (hipStream_t)stream, level, count, get);
+}
+
+int run_trlwe_ops(int device, void* stream, const GateRef* g, size_t n)
+{
+    if (g_param_set >= 0) return run_trlwe_ops_ps((int)g_param_set, device, stream, g, n);
+    if (int rc = use_device(device)) return rc;
+    return lower_trlwe_ops(BasePath{g_dev[device]}, (hipStream_t)stream, g, n);
+}
+
+// The direct batch entry points (cufhe_amd_{,ps_,lvl2_}blind_rotate_batch / keyswitch_batch): descriptor g = make(g) for each
+// ciphertext, uploaded through the stream's workspace, then one call of `launch` on the device copy
+template <class Make, class Launch>
+int direct_batch(DeviceState& s, hipStream_t st, size_t count, Make make, Launch launch)
+{
+    using Desc = decltype(make(size_t{0}));
+    std::vector<Desc> h(count);
+    for (size_t g = 0; g < count; g++) h[g] = make(g);
+    Scratch sc;
+    if (int rc = open_scratch(s, st, count * sizeof(Desc) + 4096, &sc)) return rc;
+    Desc* d;
+    if (int rc = upload_descs(s, sc, h, &d)) return rc;
+    return launch(d);
+}
+
+// A device allocation of an Initialize call (through init_malloc, on the current device): freed on that device when the owner goes
+// out of scope, unless release() has handed it over first -- a failure on the way leaves nothing allocated
+template <class T>
+struct DevPtr {
+    T* p = nullptr;
+    int phys = 0;
+    DevPtr() = default;
+    DevPtr(const DevPtr&) = delete;
+    DevPtr& operator=(const DevPtr&) = delete;
+    hipError_t alloc(size_t n)
+    {
+        if (hipError_t e = hipGetDevice(&phys)) return e;
+        return init_malloc((void**)&p, n * sizeof(T));
+    }
+    T* release() { T* r = p; p = nullptr; return r; }
+    ~DevPtr()
+    {
+        if (!p) return;
+        (void)hipSetDevice(phys);
+        (void)hipFree(p);
+    }
+};
+
+// A key-switching key of `rows` rows of row_words words, uploaded with every row padded to row_pad words (zeros) for the
+// shared-table key switch (keyswitch_kernel)
+int upload_ksk_padded(DevPtr<uint32_t>& d, const uint32_t* ksk, size_t rows, size_t row_words, size_t row_pad)
+{
+    HIP_TRY(d.alloc(rows * row_pad));
+    HIP_TRY(hipMemset(d.p, 0, rows * row_pad * sizeof(uint32_t)));
+    HIP_TRY(hipMemcpy2D(d.p, row_pad * sizeof(uint32_t), ksk, row_words * sizeof(uint32_t), row_words * sizeof(uint32_t), rows,
+                        hipMemcpyHostToDevice));
+    return 0;
 }
 
 }  // namespace
@@ -1026,37 +1120,21 @@ int cufhe_amd_initialize(const uint32_t* bk, size_t bk_words, const uint32_t* ks
     // Build first, swap last: the new keys of EVERY device are allocated and converted beside whatever is loaded; only when all of that
     // has succeeded do they replace the old ones.  A failure on the way (a full device: 104 MB per replica) frees what this call
     // allocated and leaves every device with the keys -- and the results -- it had.
-    struct Built { double* bk_ntt = nullptr; uint32_t* ksk = nullptr; uint32_t* d_bk = nullptr; };
-    std::vector<Built> built((size_t)g_gpu_num);
-    struct Undo {
-        std::vector<Built>& b; bool armed = true;
-        ~Undo()
-        {
-            for (size_t i = 0; i < b.size(); i++) {
-                if (!b[i].bk_ntt && !b[i].ksk && !b[i].d_bk) continue;
-                (void)hipSetDevice(phys_device((int)i));
-                (void)hipFree(b[i].d_bk);
-                if (armed) { (void)hipFree(b[i].bk_ntt); (void)hipFree(b[i].ksk); }
-            }
-        }
-    } undo{built};
+    struct Built { DevPtr<double> bk_ntt; DevPtr<uint32_t> ksk, d_bk; };
+    std::vector<Built> built((size_t)g_gpu_num);      // the torus-domain staging copies d_bk are freed on every return
     for (int i = 0; i < g_gpu_num; i++) {
         if (int rc = ensure_ntt(i)) return rc;
         DeviceState& s = g_dev[i];
         Built& b = built[(size_t)i];
         HIP_TRY(hipSetDevice(phys_device(i)));
-        HIP_TRY(init_malloc((void**)&b.bk_ntt, want_bk * sizeof(double)));
-        const size_t ksk_rows = want_ksk / kKsRowWords;
-        HIP_TRY(init_malloc((void**)&b.ksk, ksk_rows * kKsRowPad * sizeof(uint32_t)));
-        HIP_TRY(init_malloc((void**)&b.d_bk, want_bk * sizeof(uint32_t)));
-        HIP_TRY(hipMemcpy(b.d_bk, bk, want_bk * sizeof(uint32_t), hipMemcpyHostToDevice));
+        HIP_TRY(b.bk_ntt.alloc(want_bk));
         // KeySwitchingKeyToDevice (src/keyswitch_gpu.cu:6-16), rows padded 631 -> 640 words
-        HIP_TRY(hipMemset(b.ksk, 0, ksk_rows * kKsRowPad * sizeof(uint32_t)));
-        HIP_TRY(hipMemcpy2D(b.ksk, kKsRowPad * sizeof(uint32_t), ksk, kKsRowWords * sizeof(uint32_t),
-                            kKsRowWords * sizeof(uint32_t), ksk_rows, hipMemcpyHostToDevice));
+        if (int rc = upload_ksk_padded(b.ksk, ksk, want_ksk / kKsRowWords, kKsRowWords, kKsRowPad)) return rc;
+        HIP_TRY(b.d_bk.alloc(want_bk));
+        HIP_TRY(hipMemcpy(b.d_bk.p, bk, want_bk * sizeof(uint32_t), hipMemcpyHostToDevice));
         const size_t polys = want_bk / kN;
         const unsigned blocks = (unsigned)((polys + kNttWavesPerBlock - 1) / kNttWavesPerBlock);
-        hipLaunchKernelGGL(bk_to_ntt_kernel, dim3(blocks), dim3(kNttThreads), kNttLdsBytes, 0, b.bk_ntt, b.d_bk,
+        hipLaunchKernelGGL(bk_to_ntt_kernel, dim3(blocks), dim3(kNttThreads), kNttLdsBytes, 0, b.bk_ntt.p, b.d_bk.p,
                            polys, s.tables, n_inverse_balanced());
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipDeviceSynchronize());        // also: nothing on this device still reads the keys that are about to go
@@ -1065,11 +1143,10 @@ int cufhe_amd_initialize(const uint32_t* bk, size_t bk_words, const uint32_t* ks
         DeviceState& s = g_dev[i];
         (void)hipSetDevice(phys_device(i));
         if (s.keys_ready) { (void)hipFree(s.bk_ntt); (void)hipFree(s.ksk); }
-        s.bk_ntt = built[(size_t)i].bk_ntt;
-        s.ksk = built[(size_t)i].ksk;
+        s.bk_ntt = built[(size_t)i].bk_ntt.release();
+        s.ksk = built[(size_t)i].ksk.release();
         s.keys_ready = true;
     }
-    undo.armed = false;        // the guard still frees the torus-domain staging copies
     return 0;
 }
 
@@ -1281,13 +1358,8 @@ int cufhe_amd_blind_rotate_batch(int device, void* stream, size_t count, const u
     if (!tlwe0 || !acc) return fail(-1, "null pointer");
     if (steps < 0 || steps > kLvl0N) steps = kLvl0N;
     hipStream_t st = (hipStream_t)stream;
-    std::vector<LinDesc> rot(count);
-    for (size_t g = 0; g < count; g++) rot[g] = {tlwe0 + g * kLvl0Words, tlwe0 + g * kLvl0Words, nullptr, 1, 0, 0u, 0u};
-    Scratch sc;
-    if (int rc = open_scratch(s, st, count * sizeof(LinDesc) + 4096, &sc)) return rc;
-    LinDesc* d;
-    if (int rc = upload_descs(s, sc, rot, &d)) return rc;
-    return launch_blind_rotate(s, st, d, count, steps, acc);
+    return direct_batch(s, st, count, [&](size_t g) { return LinDesc{tlwe0 + g * kLvl0Words, tlwe0 + g * kLvl0Words, nullptr, 1, 0, 0u, 0u}; },
+                        [&](const LinDesc* d) { return launch_blind_rotate(s, st, d, count, steps, acc); });
 }
 
 int cufhe_amd_keyswitch_batch(int device, void* stream, size_t count, const uint32_t* tlwe1, uint32_t* tlwe0)
@@ -1297,14 +1369,8 @@ int cufhe_amd_keyswitch_batch(int device, void* stream, size_t count, const uint
     if (!s.keys_ready) return fail(-3, "Initialize(ek) has not been called for this device");
     if (!tlwe0 || !tlwe1) return fail(-1, "null pointer");
     hipStream_t st = (hipStream_t)stream;
-    std::vector<LinDesc> ks(count);
-    for (size_t g = 0; g < count; g++)
-        ks[g] = {tlwe1 + g * kLvl1Words, tlwe1 + g * kLvl1Words, tlwe0 + g * kLvl0Words, 1, 0, 0u, 0u};
-    Scratch sc;
-    if (int rc = open_scratch(s, st, count * sizeof(LinDesc) + 4096, &sc)) return rc;
-    LinDesc* d;
-    if (int rc = upload_descs(s, sc, ks, &d)) return rc;
-    return launch_keyswitch(s, st, d, count);
+    return direct_batch(s, st, count, [&](size_t g) { return LinDesc{tlwe1 + g * kLvl1Words, tlwe1 + g * kLvl1Words, tlwe0 + g * kLvl0Words, 1, 0, 0u, 0u}; },
+                        [&](const LinDesc* d) { return launch_keyswitch(s, st, d, count); });
 }
 
 int cufhe_amd_trgsw_to_ntt_batch(int device, void* stream, size_t count, const uint32_t* trgsw, double* trgsw_ntt)

@@ -81,20 +81,18 @@ int ensure_bk2_half_layout(DeviceState& s)
     if (s.bk2_ntt) return 0;
     if (g_bk2_host.empty()) return fail(-3, "cufhe_amd_lvl2_initialize has not been called");
     const size_t want_bk = g_bk2_host.size();
-    uint64_t* d_bk = nullptr;
-    double* half = nullptr;
-    struct Undo { uint64_t*& d; double*& h; bool armed = true; ~Undo() { (void)hipFree(d); if (armed) (void)hipFree(h); } } undo{d_bk, half};
-    HIP_TRY(init_malloc((void**)&half, (size_t)kLvl0N * k2BkStepDoubles * sizeof(double)));
-    HIP_TRY(init_malloc((void**)&d_bk, want_bk * sizeof(uint64_t)));
-    HIP_TRY(hipMemcpy(d_bk, g_bk2_host.data(), want_bk * sizeof(uint64_t), hipMemcpyHostToDevice));
+    DevPtr<double> half;
+    DevPtr<uint64_t> d_bk;            // the torus-domain staging copy: freed on every return
+    HIP_TRY(half.alloc((size_t)kLvl0N * k2BkStepDoubles));
+    HIP_TRY(d_bk.alloc(want_bk));
+    HIP_TRY(hipMemcpy(d_bk.p, g_bk2_host.data(), want_bk * sizeof(uint64_t), hipMemcpyHostToDevice));
     const size_t polys = want_bk / k2N, waves = polys * k2Limbs;
     const unsigned blocks = (unsigned)((waves + kNttWavesPerBlock - 1) / kNttWavesPerBlock);
     hipLaunchKernelGGL(bk2_to_ntt_kernel, dim3(blocks), dim3(kNttThreads), kNttWavesPerBlock * kTileBytes, 0,
-                       half, d_bk, polys, s.tables2, balanced(powmod_u64(k2N, fpf::P_U64 - 2)));
+                       half.p, d_bk.p, polys, s.tables2, balanced(powmod_u64(k2N, fpf::P_U64 - 2)));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());        // complete before any stream's kernel reads it
-    undo.armed = false;
-    s.bk2_ntt = half;
+    s.bk2_ntt = half.release();
     return 0;
 }
 
@@ -107,12 +105,8 @@ void lvl2_release_host_key()
 int launch_blind_rotate_lvl2(DeviceState& s, hipStream_t st, const RotDesc2* d, size_t count, int steps, uint64_t* acc_dump)
 {
     if (count == 0) return 0;
-    EventPair ev{};
-    if (s.profiling) {
-        HIP_TRY(hipEventCreate(&ev.a));
-        HIP_TRY(hipEventCreate(&ev.b));
-        HIP_TRY(hipEventRecord(ev.a, st));
-    }
+    ProfScope prof{s, st, count, false};
+    if (int rc = prof.begin()) return rc;
     const bool quarters = g_lvl2_kernel < 0 ? (long)count > (cus_of(s) > 0 ? cus_of(s) : 256) : g_lvl2_kernel == 1;
     if (quarters) {
         // four quarter waves per rotation, two rotations per CU (kernels_lvl2q.hip.h)
@@ -132,24 +126,14 @@ int launch_blind_rotate_lvl2(DeviceState& s, hipStream_t st, const RotDesc2* d, 
                            s.bk2_ntt, s.tables2, steps, acc_dump);
     }
     HIP_TRY(hipGetLastError());
-    if (s.profiling) {
-        HIP_TRY(hipEventRecord(ev.b, st));
-        ev.units = count;
-        std::lock_guard<std::mutex> lk(s.staging_mu);
-        s.br_events.push_back(ev);
-    }
-    return 0;
+    return prof.commit();
 }
 
 int launch_keyswitch_lvl2(DeviceState& s, hipStream_t st, const LinDesc64* d, size_t count)
 {
     if (count == 0) return 0;
-    EventPair ev{};
-    if (s.profiling) {
-        HIP_TRY(hipEventCreate(&ev.a));
-        HIP_TRY(hipEventCreate(&ev.b));
-        HIP_TRY(hipEventRecord(ev.a, st));
-    }
+    ProfScope prof{s, st, count, true};
+    if (int rc = prof.begin()) return rc;
     // keyswitch_kernel over the lvl20 shape (j cut into runs that fill the CUs) at any count; the workgroup-per-ciphertext kernel
     // (2.1 us per ciphertext) only by "ks_wg_threshold"
     if (g_ks_wg_threshold > 0 && (long)count <= g_ks_wg_threshold) {
@@ -158,80 +142,28 @@ int launch_keyswitch_lvl2(DeviceState& s, hipStream_t st, const LinDesc64* d, si
         if (int rc = launch_keyswitch_shared<KsShapeLvl2>(s, st, d, count, s.ksk2, &s.ks2_lds_opt_in)) return rc;
     }
     HIP_TRY(hipGetLastError());
-    if (s.profiling) {
-        HIP_TRY(hipEventRecord(ev.b, st));
-        ev.units = count;
-        std::lock_guard<std::mutex> lk(s.staging_mu);
-        s.ks_events.push_back(ev);
-    }
-    return 0;
+    return prof.commit();
 }
+
+// The N = 2048 ring for lower_gates (capi.hip): gates on lvl0 ciphertexts only, lvl2 TLWEs between rotation and key switch
+struct Lvl2Path {
+    using RotD = RotDesc2;
+    using KsD = LinDesc64;
+    using Mid = uint64_t;
+    static constexpr int lvl0_words = kLvl0Words, mid_words = k2Words, n = kLvl0N;
+    static constexpr uint64_t ks_mu = k2Mu;
+    static constexpr bool lvl1_gates = false;
+    DeviceState& s;
+    int ready() const { return s.keys2_ready ? 0 : fail(-3, "cufhe_amd_lvl2_initialize has not been called for this device"); }
+    int rotate(hipStream_t st, const RotDesc2* d, size_t count, int steps, uint64_t* dump) const { return launch_blind_rotate_lvl2(s, st, d, count, steps, dump); }
+    int keyswitch(hipStream_t st, const LinDesc64* d, size_t count) const { return launch_keyswitch_lvl2(s, st, d, count); }
+};
 
 template <class GetGate>
 int run_gates_lvl2(int device, void* stream, size_t count, GetGate get)
 {
     if (int rc = use_device(device)) return rc;
-    DeviceState& s = g_dev[device];
-    if (!s.keys2_ready) return fail(-3, "cufhe_amd_lvl2_initialize has not been called for this device");
-    if (count == 0) return 0;
-    hipStream_t st = (hipStream_t)stream;
-    const uint32_t negmu = 0u - kMu;
-
-    size_t nrot = 0;
-    for (size_t g = 0; g < count; g++) {
-        const int op = get(g).op;
-        if (op < 0 || op >= CUFHE_AMD_NUM_OPS) return fail(-1, "unknown gate op");
-        if (op == CUFHE_AMD_MUX || op == CUFHE_AMD_NMUX) nrot += 2;
-        else if (op < CUFHE_AMD_MUX) nrot += 1;
-    }
-    Scratch sc;
-    {
-        const size_t need = nrot * k2Words * sizeof(uint64_t) + nrot * sizeof(RotDesc2) +
-                            count * (sizeof(LinDesc64) + sizeof(LinDesc)) + 8192;
-        if (int rc = open_scratch(s, st, need, &sc)) return rc;
-    }
-    uint64_t* tmp2 = nullptr;                 // one lvl2 TLWE per rotation
-    if (nrot)
-        if (int rc = sc.alloc((void**)&tmp2, nrot * k2Words * sizeof(uint64_t))) return rc;
-    std::vector<RotDesc2> rot;
-    std::vector<LinDesc64> ks;
-    std::vector<LinDesc> lin;
-    rot.reserve(nrot); ks.reserve(count); lin.reserve(count);
-    size_t ir = 0;
-    for (size_t g = 0; g < count; g++) {
-        const GateRef gr = get(g);
-        if (!gr.out || !gr.in0) return fail(-1, "null ciphertext pointer");
-        if (gr.op == CUFHE_AMD_NOT || gr.op == CUFHE_AMD_COPY) {
-            lin.push_back({gr.in0, gr.in0, gr.out, gr.op == CUFHE_AMD_NOT ? -1 : 1, 0, 0u, 0u});
-            continue;
-        }
-        if (!gr.in1) return fail(-1, "gate needs a second operand");
-        if (gr.op == CUFHE_AMD_MUX || gr.op == CUFHE_AMD_NMUX) {
-            if (!gr.in2) return fail(-1, "mux needs a third operand");
-            uint64_t* ta = tmp2 + (ir + 0) * k2Words;
-            uint64_t* tb = tmp2 + (ir + 1) * k2Words;
-            const bool neg = gr.op == CUFHE_AMD_NMUX;
-            rot.push_back({gr.in0, gr.in1, ta, 1, 1, negmu, 0u});
-            rot.push_back({gr.in0, gr.in2, tb, -1, 1, negmu, 0u});
-            ks.push_back({ta, tb, gr.out, neg ? -1 : 1, neg ? -1 : 1, neg ? 0ull - k2Mu : k2Mu});
-            ir += 2;
-            continue;
-        }
-        uint64_t* t = tmp2 + ir * k2Words;
-        rot.push_back({gr.in0, gr.in1, t, kGateTab[gr.op][0], kGateTab[gr.op][1], (uint32_t)kGateTab[gr.op][2] * kMu, 0u});
-        ks.push_back({t, t, gr.out, 1, 0, 0ull});
-        ir += 1;
-    }
-    RotDesc2* drot;
-    LinDesc64* dks;
-    LinDesc* dlin;
-    if (int rc = upload_descs(s, sc, rot, &drot)) return rc;
-    if (int rc = upload_descs(s, sc, ks, &dks)) return rc;
-    if (int rc = upload_descs(s, sc, lin, &dlin)) return rc;
-    if (int rc = launch_blind_rotate_lvl2(s, st, drot, rot.size(), kLvl0N, nullptr)) return rc;
-    if (int rc = launch_keyswitch_lvl2(s, st, dks, ks.size())) return rc;
-    if (int rc = launch_lincomb(st, dlin, lin.size(), kLvl0Words)) return rc;
-    return 0;
+    return lower_gates(Lvl2Path{g_dev[device]}, (hipStream_t)stream, 0, count, get);
 }
 
 }  // namespace
@@ -261,38 +193,22 @@ int cufhe_amd_lvl2_initialize(const uint64_t* bk, size_t bk_words, const uint32_
     if (ksk_words != want_ksk) return fail(-1, "lvl20 key-switching key has the wrong size for this parameter set");
     // build first, swap last (as cufhe_amd_initialize): the quarter-transform layout and the key-switching key of every device beside
     // what is loaded; the half-transform layout follows on first use (ensure_bk2_half_layout)
-    struct Built { double* bk2q = nullptr; uint32_t* ksk2 = nullptr; uint64_t* d_bk = nullptr; };
-    std::vector<Built> built((size_t)g_gpu_num);
-    struct Undo {
-        std::vector<Built>& b; bool armed = true;
-        ~Undo()
-        {
-            for (size_t i = 0; i < b.size(); i++) {
-                if (!b[i].bk2q && !b[i].ksk2 && !b[i].d_bk) continue;
-                (void)hipSetDevice(phys_device((int)i));
-                (void)hipFree(b[i].d_bk);
-                if (armed) { (void)hipFree(b[i].bk2q); (void)hipFree(b[i].ksk2); }
-            }
-        }
-    } undo{built};
+    struct Built { DevPtr<double> bk2q; DevPtr<uint32_t> ksk2; DevPtr<uint64_t> d_bk; };
+    std::vector<Built> built((size_t)g_gpu_num);      // the torus-domain staging copies d_bk are freed on every return
     for (int i = 0; i < g_gpu_num; i++) {
         if (int rc = ensure_tables_lvl2(i)) return rc;
         DeviceState& s = g_dev[i];
         Built& b = built[(size_t)i];
         HIP_TRY(hipSetDevice(phys_device(i)));
-        HIP_TRY(init_malloc((void**)&b.bk2q, (size_t)kLvl0N * k2BkStepDoubles * sizeof(double)));
-        const size_t ksk_rows = want_ksk / kKsRowWords;
-        HIP_TRY(init_malloc((void**)&b.ksk2, ksk_rows * kKsRowPad * sizeof(uint32_t)));
-        HIP_TRY(hipMemset(b.ksk2, 0, ksk_rows * kKsRowPad * sizeof(uint32_t)));
-        HIP_TRY(hipMemcpy2D(b.ksk2, kKsRowPad * sizeof(uint32_t), ksk, kKsRowWords * sizeof(uint32_t),
-                            kKsRowWords * sizeof(uint32_t), ksk_rows, hipMemcpyHostToDevice));
-        HIP_TRY(init_malloc((void**)&b.d_bk, want_bk * sizeof(uint64_t)));
-        HIP_TRY(hipMemcpy(b.d_bk, bk, want_bk * sizeof(uint64_t), hipMemcpyHostToDevice));
+        HIP_TRY(b.bk2q.alloc((size_t)kLvl0N * k2BkStepDoubles));
+        if (int rc = upload_ksk_padded(b.ksk2, ksk, want_ksk / kKsRowWords, kKsRowWords, kKsRowPad)) return rc;
+        HIP_TRY(b.d_bk.alloc(want_bk));
+        HIP_TRY(hipMemcpy(b.d_bk.p, bk, want_bk * sizeof(uint64_t), hipMemcpyHostToDevice));
         const size_t polys = want_bk / k2N;
         const size_t waves = polys * k2Limbs;
         const unsigned blocks = (unsigned)((waves + kNttWavesPerBlock - 1) / kNttWavesPerBlock);
         hipLaunchKernelGGL(bk2q_to_ntt_kernel, dim3(blocks), dim3(kNttThreads), kNttWavesPerBlock * kTile512Bytes, 0,
-                           b.bk2q, b.d_bk, polys, s.tables2q, balanced(powmod_u64(k2N, fpf::P_U64 - 2)));
+                           b.bk2q.p, b.d_bk.p, polys, s.tables2q, balanced(powmod_u64(k2N, fpf::P_U64 - 2)));
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipDeviceSynchronize());        // also: nothing on this device still reads the keys that are about to go
     }
@@ -305,12 +221,11 @@ int cufhe_amd_lvl2_initialize(const uint64_t* bk, size_t bk_words, const uint32_
             if (s.keys2_ready) { (void)hipFree(s.bk2q_ntt); (void)hipFree(s.ksk2); }
             (void)hipFree(s.bk2_ntt);          // the half layout of the OLD key, if it was ever built
             s.bk2_ntt = nullptr;
-            s.bk2q_ntt = built[(size_t)i].bk2q;
-            s.ksk2 = built[(size_t)i].ksk2;
+            s.bk2q_ntt = built[(size_t)i].bk2q.release();
+            s.ksk2 = built[(size_t)i].ksk2.release();
             s.keys2_ready = true;
         }
     }
-    undo.armed = false;        // the guard still frees the torus-domain staging copies
     return 0;
 }
 
@@ -333,13 +248,8 @@ int cufhe_amd_lvl2_blind_rotate_batch(int device, void* stream, size_t count, co
     if (!tlwe0 || !acc) return fail(-1, "null pointer");
     if (steps < 0 || steps > kLvl0N) steps = kLvl0N;
     hipStream_t st = (hipStream_t)stream;
-    std::vector<RotDesc2> rot(count);
-    for (size_t g = 0; g < count; g++) rot[g] = {tlwe0 + g * kLvl0Words, tlwe0 + g * kLvl0Words, nullptr, 1, 0, 0u, 0u};
-    Scratch sc;
-    if (int rc = open_scratch(s, st, count * sizeof(RotDesc2) + 4096, &sc)) return rc;
-    RotDesc2* d;
-    if (int rc = upload_descs(s, sc, rot, &d)) return rc;
-    return launch_blind_rotate_lvl2(s, st, d, count, steps, acc);
+    return direct_batch(s, st, count, [&](size_t g) { return RotDesc2{tlwe0 + g * kLvl0Words, tlwe0 + g * kLvl0Words, nullptr, 1, 0, 0u, 0u}; },
+                        [&](const RotDesc2* d) { return launch_blind_rotate_lvl2(s, st, d, count, steps, acc); });
 }
 
 int cufhe_amd_lvl2_keyswitch_batch(int device, void* stream, size_t count, const uint64_t* tlwe2, uint32_t* tlwe0)
@@ -349,13 +259,8 @@ int cufhe_amd_lvl2_keyswitch_batch(int device, void* stream, size_t count, const
     if (!s.keys2_ready) return fail(-3, "cufhe_amd_lvl2_initialize has not been called for this device");
     if (!tlwe0 || !tlwe2) return fail(-1, "null pointer");
     hipStream_t st = (hipStream_t)stream;
-    std::vector<LinDesc64> ks(count);
-    for (size_t g = 0; g < count; g++) ks[g] = {tlwe2 + g * k2Words, tlwe2 + g * k2Words, tlwe0 + g * kLvl0Words, 1, 0, 0ull};
-    Scratch sc;
-    if (int rc = open_scratch(s, st, count * sizeof(LinDesc64) + 4096, &sc)) return rc;
-    LinDesc64* d;
-    if (int rc = upload_descs(s, sc, ks, &d)) return rc;
-    return launch_keyswitch_lvl2(s, st, d, count);
+    return direct_batch(s, st, count, [&](size_t g) { return LinDesc64{tlwe2 + g * k2Words, tlwe2 + g * k2Words, tlwe0 + g * kLvl0Words, 1, 0, 0ull}; },
+                        [&](const LinDesc64* d) { return launch_keyswitch_lvl2(s, st, d, count); });
 }
 
 }  // extern "C"

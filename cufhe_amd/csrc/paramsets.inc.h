@@ -30,8 +30,8 @@ template <class PS>
 int ps_launch_keyswitch(DeviceState& s, PsState& ps, hipStream_t st, const LinDesc* d, size_t count)
 {
     if (count == 0) return 0;
-    EventPair ev{};
-    if (int rc = prof_begin(s, st, ev)) return rc;
+    ProfScope prof{s, st, count, true};
+    if (int rc = prof.begin()) return rc;
     // keyswitch_kernel over the set's shape (j cut into runs that fill the CUs) at any count; the workgroup-per-ciphertext kernel
     // only by "ks_wg_threshold" (or when the padded table could not be built)
     if (ps.ksk_padded && !(g_ks_wg_threshold > 0 && (long)count <= g_ks_wg_threshold)) {
@@ -40,27 +40,26 @@ int ps_launch_keyswitch(DeviceState& s, PsState& ps, hipStream_t st, const LinDe
         } else {
             if (int rc = launch_keyswitch_shared<KsShapePs<PS>>(s, st, d, count, ps.ksk_padded, &ps.ks_lds_opt_in)) return rc;
         }
-        HIP_TRY(hipGetLastError());
-        return prof_end(s, st, ev, count, true);
+    } else {
+        hipLaunchKernelGGL(keyswitch_ps_kernel<PS>, dim3((unsigned)count), dim3(kKsThreads), 0, st, d, (int)count, ps.ksk);
     }
-    hipLaunchKernelGGL(keyswitch_ps_kernel<PS>, dim3((unsigned)count), dim3(kKsThreads), 0, st, d, (int)count, ps.ksk);
     HIP_TRY(hipGetLastError());
-    return prof_end(s, st, ev, count, true);
+    return prof.commit();
 }
 PsState g_ps[kParamSets][kMaxLogicalDevices];
 
 PsState& ps_state(int set, int device) { return g_ps[set][device]; }
 
-template <class F>
-int ps_dispatch(int set, F f)
+// f(PS{}) for the set of index `set` in CompiledSets (capi.hip)
+template <size_t I = 0, class F>
+int ps_dispatch(int set, F&& f)
 {
-    switch (set) {
-        case 0: return f(PsDefault{});
-        case 1: return f(PsK2N512{});
-        case 2: return f(PsCggi16{});
-        case 3: return f(PsSmallMod{});
+    if constexpr (I < std::tuple_size_v<CompiledSets>) {
+        if (set == (int)I) return f(std::tuple_element_t<I, CompiledSets>{});
+        return ps_dispatch<I + 1>(set, f);
+    } else {
+        return fail(-1, "unknown parameter set");
     }
-    return fail(-1, "unknown parameter set");
 }
 
 template <class PS>
@@ -82,8 +81,8 @@ template <class PS>
 int ps_launch_blind_rotate(DeviceState& s, PsState& ps, hipStream_t st, const LinDesc* d, size_t count, int steps, uint32_t* dump)
 {
     if (count == 0) return 0;
-    EventPair ev{};
-    if (int rc = prof_begin(s, st, ev)) return rc;
+    ProfScope prof{s, st, count, false};
+    if (int rc = prof.begin()) return rc;
     if (!ps.lds_opt_in) {
         HIP_TRY(hipFuncSetAttribute((const void*)blind_rotate_ps_kernel<PS>, hipFuncAttributeMaxDynamicSharedMemorySize, PsLds<PS>::bytes));
         HIP_TRY(hipFuncSetAttribute((const void*)blind_rotate_ps_batch_kernel<PS>, hipFuncAttributeMaxDynamicSharedMemorySize, PsbLds<PS>::bytes));
@@ -100,104 +99,11 @@ int ps_launch_blind_rotate(DeviceState& s, PsState& ps, hipStream_t st, const Li
                            ps.bk_ntt, kPsWgR4 ? ps_tables_batch<PS>(s) : ps_tables<PS>(s), steps, dump);
     }
     HIP_TRY(hipGetLastError());
-    return prof_end(s, st, ev, count, false);
+    return prof.commit();
 }
 
-template <class PS, class GetGate>
-int ps_run_gates(int set, int device, void* stream, int level, size_t count, GetGate get)
-{
-    using D = PsDims<PS>;
-    if (int rc = use_device(device)) return rc;
-    DeviceState& s = g_dev[device];
-    PsState& ps = ps_state(set, device);
-    if (!ps.ready) return fail(-3, "cufhe_amd_ps_initialize has not been called for this parameter set and device");
-    if (level != 0 && level != 1) return fail(-1, "level must be 0 or 1");
-    if (count == 0) return 0;
-    hipStream_t st = (hipStream_t)stream;
-    const uint32_t negmu = 0u - kMu;
-    size_t nrot = 0;
-    for (size_t g = 0; g < count; g++) {
-        const int op = get(g).op;
-        if (op < 0 || op >= CUFHE_AMD_NUM_OPS) return fail(-1, "unknown gate op");
-        if (op == CUFHE_AMD_MUX || op == CUFHE_AMD_NMUX) nrot += 2;
-        else if (op < CUFHE_AMD_MUX) nrot += 1;
-    }
-    Scratch sc;
-    if (int rc = open_scratch(s, st, nrot * (D::lvl1_words + D::lvl0_words) * sizeof(uint32_t) + (count * 5 + 8) * sizeof(LinDesc) + 8192, &sc)) return rc;
-    uint32_t *tmp1 = nullptr, *tmp0 = nullptr;     // lvl1 / lvl0 temporaries, one per rotation
-    if (nrot) {
-        if (int rc = sc.alloc((void**)&tmp1, nrot * D::lvl1_words * sizeof(uint32_t))) return rc;
-        if (level == 1)
-            if (int rc = sc.alloc((void**)&tmp0, nrot * D::lvl0_words * sizeof(uint32_t))) return rc;
-    }
-    std::vector<LinDesc> rot, ks, lin;
-    size_t ir = 0;
-    for (size_t g = 0; g < count; g++) {
-        const GateRef gr = get(g);
-        if (!gr.out || !gr.in0) return fail(-1, "null ciphertext pointer");
-        if (gr.op == CUFHE_AMD_NOT || gr.op == CUFHE_AMD_COPY) {
-            lin.push_back({gr.in0, gr.in0, gr.out, gr.op == CUFHE_AMD_NOT ? -1 : 1, 0, 0u, 0u});
-            continue;
-        }
-        if (!gr.in1) return fail(-1, "gate needs a second operand");
-        if (gr.op == CUFHE_AMD_MUX || gr.op == CUFHE_AMD_NMUX) {
-            if (!gr.in2) return fail(-1, "mux needs a third operand");
-            uint32_t* ta = tmp1 + (ir + 0) * D::lvl1_words;
-            uint32_t* tb = tmp1 + (ir + 1) * D::lvl1_words;
-            const bool neg = gr.op == CUFHE_AMD_NMUX;
-            if (level == 0) {   // src/bootstrap_gpu.cu:515-588
-                rot.push_back({gr.in0, gr.in1, ta, 1, 1, negmu, 0u});
-                rot.push_back({gr.in0, gr.in2, tb, -1, 1, negmu, 0u});
-                ks.push_back({ta, tb, gr.out, neg ? -1 : 1, neg ? -1 : 1, neg ? negmu : kMu, 0u});
-            } else {            // src/bootstrap_gpu.cu:706-780: two key switches, two rotations, the sum of the extracted ciphertexts
-                uint32_t* t0a = tmp0 + (ir + 0) * D::lvl0_words;
-                uint32_t* t0b = tmp0 + (ir + 1) * D::lvl0_words;
-                ks.push_back({gr.in0, gr.in1, t0a, 1, 1, negmu, 0u});
-                ks.push_back({gr.in0, gr.in2, t0b, -1, 1, negmu, 0u});
-                rot.push_back({t0a, t0a, ta, 1, 0, 0u, 0u});
-                rot.push_back({t0b, t0b, tb, 1, 0, 0u, 0u});
-                lin.push_back({ta, tb, gr.out, neg ? -1 : 1, neg ? -1 : 1, neg ? negmu : kMu, 0u});
-            }
-            ir += 2;
-            continue;
-        }
-        const int ca = kGateTab[gr.op][0], cb = kGateTab[gr.op][1];
-        const uint32_t off = (uint32_t)kGateTab[gr.op][2] * kMu;
-        if (level == 0) {       // __HomGate__ br -> iks, src/bootstrap_gpu.cu:402-421
-            uint32_t* t1 = tmp1 + ir * D::lvl1_words;
-            rot.push_back({gr.in0, gr.in1, t1, ca, cb, off, 0u});
-            ks.push_back({t1, t1, gr.out, 1, 0, 0u, 0u});
-        } else {                // __HomGate__ iks -> br, src/bootstrap_gpu.cu:383-400
-            uint32_t* t0 = tmp0 + ir * D::lvl0_words;
-            ks.push_back({gr.in0, gr.in1, t0, ca, cb, off, 0u});
-            rot.push_back({t0, t0, gr.out, 1, 0, 0u, 0u});
-        }
-        ir += 1;
-    }
-    LinDesc *drot, *dks, *dlin;
-    if (int rc = upload_descs(s, sc, rot, &drot)) return rc;
-    if (int rc = upload_descs(s, sc, ks, &dks)) return rc;
-    if (int rc = upload_descs(s, sc, lin, &dlin)) return rc;
-    if (level == 0) {
-        if (int rc = ps_launch_blind_rotate<PS>(s, ps, st, drot, rot.size(), PS::n, nullptr)) return rc;
-        if (int rc = ps_launch_keyswitch<PS>(s, ps, st, dks, ks.size())) return rc;
-    } else {
-        if (int rc = ps_launch_keyswitch<PS>(s, ps, st, dks, ks.size())) return rc;
-        if (int rc = ps_launch_blind_rotate<PS>(s, ps, st, drot, rot.size(), PS::n, nullptr)) return rc;
-    }
-    return launch_lincomb(st, dlin, lin.size(), level ? D::lvl1_words : D::lvl0_words);
-}
-
-template <class GetGate>
-int run_gates_ps(int set, int device, void* stream, int level, size_t count, GetGate get)
-{
-    return ps_dispatch(set, [&](auto psx) { return ps_run_gates<decltype(psx)>(set, device, stream, level, count, get); });
-}
-
-// The TRLWE-level operations of the per-gate API on a set (run_trlwe_ops, capi.hip, over PS): lvl0 TLWE -> TRLWE
-// (__BlindRotateGlobal__, src/bootstrap_gpu.cu:317-323), TRLWE -> TRLWE (__SEIandBootstrap2TRLWE__, :325-364), TRLWE -> lvl0 TLWE
-// (__SEIandKS__, src/keyswitch_gpu.cu:26-40) as one launch sequence, and the CMUXNTT calls of the level (src/bootstrap_gpu.cu:197-285:
-// in the reference the set chosen at build time serves them too; only its small-modulus build leaves them out, src/cufhe_gates_gpu.cu:68-86).
+// CMUXNTT on a set (src/bootstrap_gpu.cu:197-285: in the reference the set chosen at build time serves it too; only its small-modulus
+// build leaves it out, src/cufhe_gates_gpu.cu:68-86)
 template <class PS>
 int ps_launch_cmux(DeviceState& s, hipStream_t st, const CmuxDesc* d, size_t count)
 {
@@ -210,90 +116,41 @@ int ps_launch_cmux(DeviceState& s, hipStream_t st, const CmuxDesc* d, size_t cou
     return 0;
 }
 
+// A parameter set for lower_gates / lower_trlwe_ops (capi.hip)
 template <class PS>
-int ps_run_trlwe_ops(int set, int device, void* stream, const GateRef* g, size_t n)
-{
+struct PsPath {
     using D = PsDims<PS>;
-    if (int rc = use_device(device)) return rc;
-    DeviceState& s = g_dev[device];
-    PsState& ps = ps_state(set, device);
-    if (n == 0) return 0;
-    hipStream_t st = (hipStream_t)stream;
-    constexpr size_t trlwe_words = (size_t)D::K1 * D::N;
-    size_t n_se = 0, n_rot = 0, n_t0 = 0, n_cmux = 0;
-    for (size_t i = 0; i < n; i++) {
-        if (!g[i].out || !g[i].in0) return fail(-1, "null operand");
-        switch (g[i].op) {
-            case CUFHE_AMD_TL_BOOTSTRAP: n_rot++; break;
-            case CUFHE_AMD_TL_REFRESH: n_se++; n_rot++; n_t0++; break;
-            case CUFHE_AMD_TL_SEIKS: n_se++; break;
-            case CUFHE_AMD_TL_CMUX:
-                if (PS::small_modulus) return fail(-1, "CMUXNTT: the small-modulus build of the reference has none (src/cufhe_gates_gpu.cu:68-86)");
-                if (!g[i].in1 || !g[i].in2) return fail(-1, "CMUXNTT: null operand");
-                n_cmux++;
-                break;
-            default: return fail(-1, "unknown TRLWE-level op");
-        }
-    }
-    if (n_cmux < n && !ps.ready) return fail(-3, "cufhe_amd_ps_initialize has not been called for this parameter set and device");
-    if (n_cmux && !s.ntt_ready) return fail(-3, "Initialize() has not been called for this device");
-    Scratch sc;
-    if (int rc = open_scratch(s, st, (n_se * D::lvl1_words + n_t0 * D::lvl0_words + n_rot * trlwe_words) * 4 + (3 * n + 8) * sizeof(LinDesc) +
-                                         n_cmux * sizeof(CmuxDesc) + 16384, &sc))
-        return rc;
-    if (n_cmux) {      // the CMUXNTT calls of this level: independent of its other operations (the scheduler's contract); needs no key
-        if constexpr (!PS::small_modulus) {
-            std::vector<CmuxDesc> cm;
-            cm.reserve(n_cmux);
-            for (size_t i = 0; i < n; i++)
-                if (g[i].op == CUFHE_AMD_TL_CMUX) cm.push_back({g[i].in0, g[i].in1, g[i].out, (const double*)g[i].in2});
-            CmuxDesc* dcm;
-            if (int rc = upload_descs(s, sc, cm, &dcm)) return rc;
-            if (int rc = ps_launch_cmux<PS>(s, st, dcm, cm.size())) return rc;
-        }
-        if (n_cmux == n) return 0;
-    }
-    uint32_t *t1 = nullptr, *t0 = nullptr, *dump = nullptr;
-    if (n_se) if (int rc = sc.alloc((void**)&t1, n_se * D::lvl1_words * 4)) return rc;
-    if (n_t0) if (int rc = sc.alloc((void**)&t0, n_t0 * D::lvl0_words * 4)) return rc;
-    if (n_rot) if (int rc = sc.alloc((void**)&dump, n_rot * trlwe_words * 4)) return rc;
-    std::vector<LinDesc> se, ks, rot, scat;
-    size_t i_se = 0, i_t0 = 0, i_rot = 0;
-    for (size_t i = 0; i < n; i++) {
-        if (g[i].op == CUFHE_AMD_TL_CMUX) continue;
-        if (g[i].op == CUFHE_AMD_TL_BOOTSTRAP) {
-            rot.push_back({g[i].in0, g[i].in0, nullptr, 1, 0, 0u, 0u});
-        } else {
-            uint32_t* a = t1 + i_se++ * D::lvl1_words;
-            se.push_back({g[i].in0, g[i].in0, a, 1, 0, 0u, 0u});
-            if (g[i].op == CUFHE_AMD_TL_SEIKS) {
-                ks.push_back({a, a, g[i].out, 1, 0, 0u, 0u});
-                continue;
-            }
-            uint32_t* b = t0 + i_t0++ * D::lvl0_words;
-            ks.push_back({a, a, b, 1, 0, 0u, 0u});
-            rot.push_back({b, b, nullptr, 1, 0, 0u, 0u});
-        }
-        uint32_t* d = dump + i_rot++ * trlwe_words;
-        scat.push_back({d, d, g[i].out, 1, 0, 0u, 0u});
-    }
-    LinDesc *dse, *dks, *drot, *dscat;
-    if (int rc = upload_descs(s, sc, se, &dse)) return rc;
-    if (int rc = upload_descs(s, sc, ks, &dks)) return rc;
-    if (int rc = upload_descs(s, sc, rot, &drot)) return rc;
-    if (int rc = upload_descs(s, sc, scat, &dscat)) return rc;
-    if (!se.empty()) {
-        hipLaunchKernelGGL(sample_extract_ps_kernel<PS>, dim3((unsigned)(se.size() < 2048 ? se.size() : 2048)), dim3(256), 0, st, dse, (int)se.size());
-        HIP_TRY(hipGetLastError());
-    }
-    if (int rc = ps_launch_keyswitch<PS>(s, ps, st, dks, ks.size())) return rc;
-    if (int rc = ps_launch_blind_rotate<PS>(s, ps, st, drot, rot.size(), PS::n, dump)) return rc;
-    return launch_lincomb(st, dscat, scat.size(), (int)trlwe_words);
+    using RotD = LinDesc;
+    using KsD = LinDesc;
+    using Mid = uint32_t;
+    static constexpr int lvl0_words = D::lvl0_words, mid_words = D::lvl1_words, n = PS::n;
+    static constexpr uint32_t ks_mu = kMu;
+    static constexpr bool lvl1_gates = true, has_cmux = !PS::small_modulus;
+    static constexpr size_t trlwe_words = (size_t)D::K1 * D::N;
+    static constexpr auto se_kernel = sample_extract_ps_kernel<PS>;
+    DeviceState& s;
+    PsState& ps;
+    int ready() const { return ps.ready ? 0 : fail(-3, "cufhe_amd_ps_initialize has not been called for this parameter set and device"); }
+    int rotate(hipStream_t st, const LinDesc* d, size_t count, int steps, uint32_t* dump) const { return ps_launch_blind_rotate<PS>(s, ps, st, d, count, steps, dump); }
+    int keyswitch(hipStream_t st, const LinDesc* d, size_t count) const { return ps_launch_keyswitch<PS>(s, ps, st, d, count); }
+    int cmux(hipStream_t st, const CmuxDesc* d, size_t count) const { return ps_launch_cmux<PS>(s, st, d, count); }
+};
+
+template <class GetGate>
+int run_gates_ps(int set, int device, void* stream, int level, size_t count, GetGate get)
+{
+    return ps_dispatch(set, [&](auto psx) -> int {
+        if (int rc = use_device(device)) return rc;
+        return lower_gates(PsPath<decltype(psx)>{g_dev[device], ps_state(set, device)}, (hipStream_t)stream, level, count, get);
+    });
 }
 
 int run_trlwe_ops_ps(int set, int device, void* stream, const GateRef* g, size_t n)
 {
-    return ps_dispatch(set, [&](auto psx) { return ps_run_trlwe_ops<decltype(psx)>(set, device, stream, g, n); });
+    return ps_dispatch(set, [&](auto psx) -> int {
+        if (int rc = use_device(device)) return rc;
+        return lower_trlwe_ops(PsPath<decltype(psx)>{g_dev[device], ps_state(set, device)}, (hipStream_t)stream, g, n);
+    });
 }
 
 // words of a level-0 / level-1 ciphertext, (level 2) a TRLWE or (level 3) a TRGSW in the NTT domain (uint32 words: two per double) of a set
@@ -394,42 +251,24 @@ int cufhe_amd_ps_initialize(int set, const uint32_t* bk, size_t bk_words, const 
         if (bk_words != D::bk_words) return fail(-1, "bootstrapping key has the wrong size for this parameter set");
         if (ksk_words != D::ksk_words) return fail(-1, "key-switching key has the wrong size for this parameter set");
         // build first, swap last (as cufhe_amd_initialize): a failure leaves every device with the keys of this set it had
-        std::vector<PsState> built((size_t)g_gpu_num);
-        std::vector<uint32_t*> d_bk((size_t)g_gpu_num, nullptr);
-        struct Undo {
-            std::vector<PsState>& b; std::vector<uint32_t*>& d; bool armed = true;
-            ~Undo()
-            {
-                for (size_t i = 0; i < b.size(); i++) {
-                    if (!d[i] && !b[i].bk_ntt && !b[i].ksk && !b[i].ksk_padded) continue;
-                    (void)hipSetDevice(phys_device((int)i));
-                    (void)hipFree(d[i]);
-                    if (armed) { (void)hipFree(b[i].bk_ntt); (void)hipFree(b[i].ksk); (void)hipFree(b[i].ksk_padded); }
-                }
-            }
-        } undo{built, d_bk};
+        struct Built { DevPtr<double> bk_ntt; DevPtr<uint32_t> ksk, ksk_padded, d_bk; };
+        std::vector<Built> built((size_t)g_gpu_num);      // the torus-domain staging copies d_bk are freed on every return
         for (int i = 0; i < g_gpu_num; i++) {
             if (int rc = ensure_ntt(i)) return rc;
             DeviceState& s = g_dev[i];
-            PsState& ps = built[(size_t)i];
+            Built& b = built[(size_t)i];
             HIP_TRY(hipSetDevice(phys_device(i)));
-            HIP_TRY(init_malloc((void**)&ps.bk_ntt, (size_t)PS::n * D::bk_ntt_step_doubles * sizeof(double)));
-            HIP_TRY(init_malloc((void**)&ps.ksk, D::ksk_words * sizeof(uint32_t)));
-            HIP_TRY(hipMemcpy(ps.ksk, ksk, D::ksk_words * sizeof(uint32_t), hipMemcpyHostToDevice));
-            {      // the same table with rows padded to a multiple of 64 words, for the shared-table kernels
-                constexpr size_t w0 = D::lvl0_words, pad = PsKs<PS>::row_pad;
-                const size_t ksk_rows = D::ksk_words / w0;
-                HIP_TRY(init_malloc((void**)&ps.ksk_padded, ksk_rows * pad * sizeof(uint32_t)));
-                HIP_TRY(hipMemset(ps.ksk_padded, 0, ksk_rows * pad * sizeof(uint32_t)));
-                HIP_TRY(hipMemcpy2D(ps.ksk_padded, pad * sizeof(uint32_t), ksk, w0 * sizeof(uint32_t), w0 * sizeof(uint32_t), ksk_rows,
-                                    hipMemcpyHostToDevice));
-            }
-            HIP_TRY(init_malloc((void**)&d_bk[(size_t)i], D::bk_words * sizeof(uint32_t)));
-            HIP_TRY(hipMemcpy(d_bk[(size_t)i], bk, D::bk_words * sizeof(uint32_t), hipMemcpyHostToDevice));
+            HIP_TRY(b.bk_ntt.alloc((size_t)PS::n * D::bk_ntt_step_doubles));
+            HIP_TRY(b.ksk.alloc(D::ksk_words));
+            HIP_TRY(hipMemcpy(b.ksk.p, ksk, D::ksk_words * sizeof(uint32_t), hipMemcpyHostToDevice));
+            // the same table with rows padded to a multiple of 64 words, for the shared-table kernels
+            if (int rc = upload_ksk_padded(b.ksk_padded, ksk, D::ksk_words / D::lvl0_words, D::lvl0_words, PsKs<PS>::row_pad)) return rc;
+            HIP_TRY(b.d_bk.alloc(D::bk_words));
+            HIP_TRY(hipMemcpy(b.d_bk.p, bk, D::bk_words * sizeof(uint32_t), hipMemcpyHostToDevice));
             const size_t polys = D::bk_words / D::N, waves = polys * PS::limbs;
             const unsigned blocks = (unsigned)((waves + kNttWavesPerBlock - 1) / kNttWavesPerBlock);
             hipLaunchKernelGGL(bk_to_ntt_ps_kernel<PS>, dim3(blocks), dim3(kNttThreads), PO::table_bytes + kNttWavesPerBlock * PO::tile_bytes, 0,
-                               ps.bk_ntt, d_bk[(size_t)i], polys, ps_tables<PS>(s), balanced(powmod_u64(D::N, fpf::P_U64 - 2)));
+                               b.bk_ntt.p, b.d_bk.p, polys, ps_tables<PS>(s), balanced(powmod_u64(D::N, fpf::P_U64 - 2)));
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipDeviceSynchronize());        // also: nothing on this device still reads the keys that are about to go
         }
@@ -441,10 +280,13 @@ int cufhe_amd_ps_initialize(int set, const uint32_t* bk, size_t bk_words, const 
                 (void)hipFree(ps.ksk);
                 if (ps.ksk_padded) (void)hipFree(ps.ksk_padded);
             }
-            ps = built[(size_t)i];
+            Built& b = built[(size_t)i];
+            ps = PsState{};
+            ps.bk_ntt = b.bk_ntt.release();
+            ps.ksk = b.ksk.release();
+            ps.ksk_padded = b.ksk_padded.release();
             ps.ready = true;
         }
-        undo.armed = false;
         return 0;
     });
 }
@@ -486,11 +328,9 @@ int cufhe_amd_ps_gate_batch_level(int set, int device, void* stream, int level, 
                                   uint32_t* out, const uint32_t* in0, const uint32_t* in1, const uint32_t* in2, size_t stride_words)
 {
     if (!ops) return fail(-1, "null ops");
-    return ps_dispatch(set, [&](auto psx) {
-        return ps_run_gates<decltype(psx)>(set, device, stream, level, count, [&](size_t g) {
-            return GateRef{ops[g * (size_t)ops_stride], out + g * stride_words, in0 ? in0 + g * stride_words : nullptr,
-                           in1 ? in1 + g * stride_words : nullptr, in2 ? in2 + g * stride_words : nullptr};
-        });
+    return run_gates_ps(set, device, stream, level, count, [&](size_t g) {
+        return GateRef{ops[g * (size_t)ops_stride], out + g * stride_words, in0 ? in0 + g * stride_words : nullptr,
+                       in1 ? in1 + g * stride_words : nullptr, in2 ? in2 + g * stride_words : nullptr};
     });
 }
 
@@ -507,18 +347,12 @@ int cufhe_amd_ps_blind_rotate_batch(int set, int device, void* stream, size_t co
     return ps_dispatch(set, [&](auto psx) -> int {
         using PS = decltype(psx);
         using D = PsDims<PS>;
-        DeviceState& s = g_dev[device];
-        PsState& ps = ps_state(set, device);
-        if (!ps.ready) return fail(-3, "cufhe_amd_ps_initialize has not been called for this parameter set and device");
+        const PsPath<PS> p{g_dev[device], ps_state(set, device)};
+        if (int rc = p.ready()) return rc;
         const int st_steps = (steps < 0 || steps > PS::n) ? PS::n : steps;
         hipStream_t st = (hipStream_t)stream;
-        std::vector<LinDesc> rot(count);
-        for (size_t g = 0; g < count; g++) rot[g] = {tlwe0 + g * D::lvl0_words, tlwe0 + g * D::lvl0_words, nullptr, 1, 0, 0u, 0u};
-        Scratch sc;
-        if (int rc = open_scratch(s, st, count * sizeof(LinDesc) + 4096, &sc)) return rc;
-        LinDesc* d;
-        if (int rc = upload_descs(s, sc, rot, &d)) return rc;
-        return ps_launch_blind_rotate<PS>(s, ps, st, d, count, st_steps, acc);
+        return direct_batch(p.s, st, count, [&](size_t g) { return LinDesc{tlwe0 + g * D::lvl0_words, tlwe0 + g * D::lvl0_words, nullptr, 1, 0, 0u, 0u}; },
+                            [&](const LinDesc* d) { return p.rotate(st, d, count, st_steps, acc); });
     });
 }
 
@@ -597,18 +431,12 @@ int cufhe_amd_ps_keyswitch_batch(int set, int device, void* stream, size_t count
     return ps_dispatch(set, [&](auto psx) -> int {
         using PS = decltype(psx);
         using D = PsDims<PS>;
-        DeviceState& s = g_dev[device];
-        PsState& ps = ps_state(set, device);
-        if (!ps.ready) return fail(-3, "cufhe_amd_ps_initialize has not been called for this parameter set and device");
+        const PsPath<PS> p{g_dev[device], ps_state(set, device)};
+        if (int rc = p.ready()) return rc;
         if (count == 0) return 0;
         hipStream_t st = (hipStream_t)stream;
-        std::vector<LinDesc> ks(count);
-        for (size_t g = 0; g < count; g++) ks[g] = {tlwe1 + g * D::lvl1_words, tlwe1 + g * D::lvl1_words, tlwe0 + g * D::lvl0_words, 1, 0, 0u, 0u};
-        Scratch sc;
-        if (int rc = open_scratch(s, st, count * sizeof(LinDesc) + 4096, &sc)) return rc;
-        LinDesc* d;
-        if (int rc = upload_descs(s, sc, ks, &d)) return rc;
-        return ps_launch_keyswitch<PS>(s, ps, st, d, count);
+        return direct_batch(p.s, st, count, [&](size_t g) { return LinDesc{tlwe1 + g * D::lvl1_words, tlwe1 + g * D::lvl1_words, tlwe0 + g * D::lvl0_words, 1, 0, 0u, 0u}; },
+                            [&](const LinDesc* d) { return p.keyswitch(st, d, count); });
     });
 }
 
