@@ -93,6 +93,8 @@ SIGNATURES = {
                                             c_void, c_void, c_void, c_void, ctypes.c_size_t]),
     "cufhe_amd_gate_list": (ctypes.c_int, [ctypes.c_int, c_void, ctypes.c_int, ctypes.c_size_t, c_void,
                                            c_void, c_void, c_void, c_void]),
+    "cufhe_amd_define_gate": (ctypes.c_int, [c_i32p, ctypes.c_uint32, c_u32p, ctypes.POINTER(ctypes.c_int)]),
+    "cufhe_amd_test_vector": (ctypes.c_int, [c_u32p, ctypes.c_int, c_u32p]),
     "cufhe_amd_ctxt_create": (ctypes.c_int, [ctypes.c_int, c_void, ctypes.POINTER(c_void)]),
     "cufhe_amd_ctxt_destroy": (ctypes.c_int, [c_void]),
     "cufhe_amd_ctxt_device_ptr": (c_void, [c_void, ctypes.c_int]),

@@ -282,6 +282,51 @@ Mux, gMux = _make3(MUX, True), _make3(MUX, False)
 NMux, gNMux = _make3(NMUX, True), _make3(NMUX, False)
 
 
+# ---- user gates: programmable bootstrapping (cufhe_amd_define_gate, include/cufhe_amd.h) ----
+USER_OP_BASE, MAX_USER_GATES = 1000, 64
+
+
+def define_gate(coeffs, offset=0, test_vector=None):
+    """A user gate x = c0 in0 + c1 in1 + c2 in2 + (0, .., 0, offset) bootstrapped through `test_vector` (N torus words; None: the
+    constant mu).  coeffs: one to three integers (missing ones are 0).  Returns the op id, usable wherever a built-in op is."""
+    c = np.zeros(3, dtype=np.int32)
+    c[:len(coeffs)] = coeffs
+    tv = None
+    if test_vector is not None:
+        tv = np.ascontiguousarray(test_vector, dtype=np.uint32)
+        if tv.size != PARAMS.N:
+            raise ValueError(f"test vector must have N = {PARAMS.N} words")
+    op = ctypes.c_int()
+    check(lib.cufhe_amd_define_gate(c.ctypes.data_as(_lib.c_i32p), int(offset) & 0xFFFFFFFF,
+                                    tv.ctypes.data_as(_lib.c_u32p) if tv is not None else None, ctypes.byref(op)))
+    return op.value
+
+
+def test_vector(values):
+    """The test vector of a function on len(values) messages (a power of two, 2 .. N/2) encoded with a padding bit, m -> m 2^32 / (2p):
+    values are the output torus words (cufhe_amd_test_vector)."""
+    v = np.ascontiguousarray(values, dtype=np.uint32)
+    tv = np.empty(PARAMS.N, dtype=np.uint32)
+    check(lib.cufhe_amd_test_vector(v.ctypes.data_as(_lib.c_u32p), int(v.size), tv.ctypes.data_as(_lib.c_u32p)))
+    return tv
+
+
+test_vector.__test__ = False      # not a pytest test where it is imported by name
+
+
+def Apply(op, out, *ins_and_st):
+    """Apply(op, out, in0[, in1[, in2]], st): a user gate (or any op) on the per-gate API, inputs from tlwehost, result delivered to
+    out's tlwehost -- the copying form, like And(..)."""
+    *ins, st = ins_and_st
+    _gate(op, True, out, ins, st)
+
+
+def gApply(op, out, *ins_and_st):
+    """gApply(op, out, in0[, in1[, in2]], st): the device-resident form, like gAnd(..)."""
+    *ins, st = ins_and_st
+    _gate(op, False, out, ins, st)
+
+
 # ---- native batched entry points (what bench.py and the parity tests drive) ----
 def gate_batch(ops, level, out, in0, in1=None, in2=None, count=None, device=0, stream=None):
     """ops: one op code or an int array of `count` codes; operands are DeviceBuffers holding

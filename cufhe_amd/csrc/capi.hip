@@ -7,6 +7,7 @@
 #include <sched.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cctype>
 #include <cstdio>
 #include <cstring>
@@ -69,6 +70,7 @@ struct DeviceState {
     Ntt512Tables* tables512 = nullptr;   // [3]: the two 512-point halves (low-latency kernel), stand-alone N = 512
     double* bk_ntt = nullptr;
     uint32_t* ksk = nullptr;
+    uint32_t* tvs = nullptr;             // [kMaxUserGates][kN]: the user gates' test vectors (cufhe_amd_define_gate); CleanUp frees it
     // device fault word: pinned, host-coherent, mapped into the device (kernels_common.hip.h: kFault*); sticky until CleanUp
     uint32_t* fault_host = nullptr;
     uint32_t* fault = nullptr;
@@ -594,7 +596,7 @@ int launch_blind_rotate(DeviceState& s, hipStream_t st, const LinDesc* d, size_t
     auto launch_batch = [&](const LinDesc* dd, size_t n, int active, uint32_t* dump) {
         const unsigned blocks = (unsigned)((n + active - 1) / active);
         hipLaunchKernelGGL(blind_rotate_kernel, dim3(blocks), dim3(kBrThreads), kBrLdsBytes, st, dd, (int)n,
-                           s.bk_ntt, s.tables_r4, steps, dump, active);
+                           s.bk_ntt, s.tables_r4, steps, dump, active, s.tvs);
     };
     // Measured on MI355X, 256 CUs (tools/latency_sweep.py, tools/ll_times.py; profiles/r02_latency_sweep.txt, r05_ll_ab.txt), ms per
     // launch of n rotations, key switch included:
@@ -608,12 +610,12 @@ int launch_blind_rotate(DeviceState& s, hipStream_t st, const LinDesc* d, size_t
     auto launch_ll = [&](const LinDesc* dd, size_t n, uint32_t* dump) {
         // smallest batches: one 16-wave workgroup per rotation, transforms split in halves (kernels_ll.hip.h)
         hipLaunchKernelGGL(blind_rotate_ll_kernel, dim3((unsigned)n), dim3(kLlThreads), kLlLdsBytes, st, dd, (int)n,
-                           s.bk_ntt, s.tables512, steps, dump);
+                           s.bk_ntt, s.tables512, steps, dump, s.tvs);
     };
     auto launch_ll2 = [&](const LinDesc* dd, size_t n, uint32_t* dump) {
         // two rotations per workgroup: the row phase of one beside the inverse transforms of the other (kernels_ll.hip.h)
         hipLaunchKernelGGL(blind_rotate_ll2_kernel, dim3((unsigned)((n + 1) / 2)), dim3(kLlThreads), kLl2LdsBytes, st, dd, (int)n,
-                           s.bk_ntt, s.tables512, steps, dump, s.fault);
+                           s.bk_ntt, s.tables512, steps, dump, s.fault, s.tvs);
     };
     auto launch_small = [&](const LinDesc* dd, size_t n, uint32_t* dump) {
         if (g_ll2_threshold > 0 && (long)n <= g_ll2_threshold) {
@@ -714,6 +716,24 @@ const int kGateTab[10][3] = {
 
 using sched::GateRef;
 
+// User gates (cufhe_amd_define_gate): definition k is op CUFHE_AMD_USER_OP_BASE + k.  A definition is written once, before
+// g_user_count is raised past it, and never changes afterwards, so the gate paths read it without a lock; its test vector is row k
+// of every device's DeviceState::tvs.  CleanUp drops them all.
+struct UserGate { int32_t c[3]; uint32_t off; bool tv; };
+static_assert(CUFHE_AMD_MAX_USER_GATES == kMaxUserGates, "the header's capacity is the device table's");
+static_assert(CUFHE_AMD_USER_OP_BASE > CUFHE_AMD_TL_CMUX, "user op ids do not overlap the built-in or TRLWE-level ops");
+UserGate g_user[kMaxUserGates];
+std::atomic<int> g_user_count{0};
+bool is_user_op(int op) { return op >= CUFHE_AMD_USER_OP_BASE && op < CUFHE_AMD_USER_OP_BASE + kMaxUserGates; }
+// the definition of `op`; nullptr when op is not a defined user gate
+const UserGate* user_gate(int op)
+{
+    const int k = op - CUFHE_AMD_USER_OP_BASE;
+    return k >= 0 && k < g_user_count.load(std::memory_order_acquire) ? &g_user[k] : nullptr;
+}
+// operands a user gate reads: in0 (c1 = c2 = 0), in0 and in1 (c2 = 0), all three
+int user_gate_arity(const UserGate& u) { return u.c[2] ? 3 : u.c[1] ? 2 : 1; }
+
 template <class GetGate>
 int run_gates_lvl2(int device, void* stream, size_t count, GetGate get);   // lvl2.inc.h
 template <class GetGate>
@@ -741,46 +761,93 @@ long g_param_set = -1;
 //   ks_mu              the mu of the Mux sum in the key switch
 //   lvl1_gates         whether it has gates on Mid ciphertexts (level 1)
 //   s, ready(), rotate(), keyswitch()   its device, the readiness check and the two launchers
+//   user_gates         whether its rotation kernels read LinDesc::pad as a test-vector row (user gates; the default path only)
 // Level 0: blind rotate -> key switch (__HomGate__ br -> iks); level 1: key switch -> blind rotate (iks -> br); Not / Copy and the
-// level-1 Mux sums run last, as one lincomb.
+// level-1 Mux sums run last, as one lincomb.  The three-input user gates' c0 in0 + c1 in1 run first, as one lincomb into temporaries.
 template <class P, class GetGate>
 int lower_gates(const P& p, hipStream_t st, int level, size_t count, GetGate get)
 {
     using Mid = typename P::Mid;
+    if constexpr (!P::user_gates) {
+        for (size_t g = 0; g < count; g++)
+            if (is_user_op(get(g).op))
+                return fail(-1, "user gates run on the default path only: not with \"param_set\" active or on the N = 2048 ring (\"lvl0_ring\")");
+    }
     if (int rc = p.ready()) return rc;
     if (level != 0 && level != 1) return fail(-1, "level must be 0 or 1");
     if (count == 0) return 0;
     const uint32_t negmu = 0u - kMu;
 
     // first pass: count temporaries
-    size_t nrot = 0;
+    size_t nrot = 0, npre = 0;
     for (size_t g = 0; g < count; g++) {
         const int op = get(g).op;
+        if (is_user_op(op)) {
+            const UserGate* u = user_gate(op);
+            if (!u) return fail(-1, "user gate op not defined (cufhe_amd_define_gate; CleanUp drops the definitions)");
+            nrot += 1;
+            if (user_gate_arity(*u) == 3) npre += 1;
+            continue;
+        }
         if (op < 0 || op >= CUFHE_AMD_NUM_OPS) return fail(-1, "unknown gate op");
         if (op == CUFHE_AMD_MUX || op == CUFHE_AMD_NMUX) nrot += 2;
         else if (op < CUFHE_AMD_MUX) nrot += 1;
     }
+    const size_t level_words = level ? P::mid_words * sizeof(Mid) / sizeof(uint32_t) : P::lvl0_words;
     Scratch sc;
     {
         const size_t desc = std::max({sizeof(typename P::RotD), sizeof(typename P::KsD), sizeof(LinDesc)});
-        const size_t need = nrot * (P::mid_words * sizeof(Mid) + P::lvl0_words * sizeof(uint32_t)) + (count * 5 + 8) * desc + 8192;
+        const size_t need = nrot * (P::mid_words * sizeof(Mid) + P::lvl0_words * sizeof(uint32_t)) + npre * level_words * sizeof(uint32_t) +
+                            (count * 6 + 8) * desc + 8192;
         if (int rc = open_scratch(p.s, st, need, &sc)) return rc;
     }
     Mid* tmp1 = nullptr;          // the rotations' results, one per rotation
     uint32_t* tmp0 = nullptr;     // level 1: the key switches' results, one per rotation
+    uint32_t* tmpp = nullptr;     // the pre-added c0 in0 + c1 in1 of the three-input user gates, at the gates' level
     if (nrot) {
         if (int rc = sc.alloc((void**)&tmp1, nrot * P::mid_words * sizeof(Mid))) return rc;
         if (level == 1)
             if (int rc = sc.alloc((void**)&tmp0, nrot * P::lvl0_words * sizeof(uint32_t))) return rc;
     }
+    if (npre)
+        if (int rc = sc.alloc((void**)&tmpp, npre * level_words * sizeof(uint32_t))) return rc;
     std::vector<typename P::RotD> rot;
     std::vector<typename P::KsD> ks;
-    std::vector<LinDesc> lin;
-    rot.reserve(count * 2); ks.reserve(count * 2); lin.reserve(count);
+    std::vector<LinDesc> lin, pre;
+    rot.reserve(count * 2); ks.reserve(count * 2); lin.reserve(count); pre.reserve(npre);
     size_t ir = 0;
     for (size_t g = 0; g < count; g++) {
         const GateRef gr = get(g);
         if (!gr.out || !gr.in0) return fail(-1, "null ciphertext pointer");
+        if constexpr (P::user_gates) {
+            if (const UserGate* u = user_gate(gr.op)) {
+                // x = c0 in0 + c1 in1 + c2 in2 + (0, ..., 0, off) through the two-input gate path; the rotation starts from the
+                // definition's test vector (LinDesc::pad = row + 1) or from mu (pad 0)
+                const int arity = user_gate_arity(*u);
+                if (arity >= 2 && !gr.in1) return fail(-1, "user gate needs a second operand");
+                if (arity == 3 && !gr.in2) return fail(-1, "user gate needs a third operand");
+                const uint32_t* a = gr.in0;
+                const uint32_t* b = arity >= 2 ? gr.in1 : gr.in0;
+                int32_t ca = u->c[0], cb = u->c[1];
+                if (arity == 3) {
+                    uint32_t* t = tmpp + pre.size() * level_words;
+                    pre.push_back({gr.in0, gr.in1, t, u->c[0], u->c[1], 0u, 0u});
+                    a = t; b = gr.in2; ca = 1; cb = u->c[2];
+                }
+                const uint32_t pad = u->tv ? (uint32_t)(gr.op - CUFHE_AMD_USER_OP_BASE) + 1 : 0u;
+                if (level == 0) {
+                    Mid* t1 = tmp1 + ir * P::mid_words;
+                    rot.push_back({a, b, t1, ca, cb, u->off, pad});
+                    ks.push_back({t1, t1, gr.out, 1, 0, 0u});
+                } else {
+                    uint32_t* t0 = tmp0 + ir * P::lvl0_words;
+                    ks.push_back({a, b, t0, ca, cb, u->off});
+                    rot.push_back({t0, t0, gr.out, 1, 0, 0u, pad});
+                }
+                ir += 1;
+                continue;
+            }
+        }
         if (gr.op == CUFHE_AMD_NOT || gr.op == CUFHE_AMD_COPY) {
             lin.push_back({gr.in0, gr.in0, gr.out, gr.op == CUFHE_AMD_NOT ? -1 : 1, 0, 0u, 0u});
             continue;
@@ -824,10 +891,12 @@ int lower_gates(const P& p, hipStream_t st, int level, size_t count, GetGate get
     // write straight to `out`; a lincomb that reads tmp1 must run after the rotations.
     typename P::RotD* drot;
     typename P::KsD* dks;
-    LinDesc* dlin;
+    LinDesc *dlin, *dpre;
     if (int rc = upload_descs(p.s, sc, rot, &drot)) return rc;
     if (int rc = upload_descs(p.s, sc, ks, &dks)) return rc;
     if (int rc = upload_descs(p.s, sc, lin, &dlin)) return rc;
+    if (int rc = upload_descs(p.s, sc, pre, &dpre)) return rc;
+    if (int rc = launch_lincomb(st, dpre, pre.size(), (int)level_words)) return rc;
     if (level == 0) {
         if (int rc = p.rotate(st, drot, rot.size(), P::n, nullptr)) return rc;
         if (int rc = p.keyswitch(st, dks, ks.size())) return rc;
@@ -931,7 +1000,7 @@ struct BasePath {
     using Mid = uint32_t;
     static constexpr int lvl0_words = kLvl0Words, mid_words = kLvl1Words, n = kLvl0N;
     static constexpr uint32_t ks_mu = kMu;
-    static constexpr bool lvl1_gates = true, has_cmux = true;
+    static constexpr bool lvl1_gates = true, has_cmux = true, user_gates = true;
     static constexpr size_t trlwe_words = 2 * kN;
     static constexpr auto se_kernel = sample_extract_desc_kernel;
     DeviceState& s;
@@ -950,6 +1019,14 @@ struct BasePath {
 template <class GetGate>
 int run_gates(int device, void* stream, int level, size_t count, GetGate get)
 {
+    // user ops are refused before any device work when they are not defined or the path they would take has no test-vector table
+    const bool user_ok = g_param_set < 0 && !(level == 0 && g_lvl0_ring == 2048);
+    for (size_t g = 0; g < count; g++) {
+        const int op = get(g).op;
+        if (!is_user_op(op)) continue;
+        if (!user_gate(op)) return fail(-1, "user gate op not defined (cufhe_amd_define_gate; CleanUp drops the definitions)");
+        if (!user_ok) return fail(-1, "user gates run on the default path only: not with \"param_set\" active or on the N = 2048 ring (\"lvl0_ring\")");
+    }
     if (level == 0 && g_lvl0_ring == 2048) return run_gates_lvl2(device, stream, count, get);
     if ((level == 0 || level == 1) && g_param_set >= 0) return run_gates_ps((int)g_param_set, device, stream, level, count, get);
     if (int rc = use_device(device)) return rc;
@@ -1167,6 +1244,7 @@ int cufhe_amd_cleanup(void)
             v->clear();
         }
         if (s.keys_ready) { HIP_TRY(hipFree(s.bk_ntt)); HIP_TRY(hipFree(s.ksk)); }
+        if (s.tvs) { HIP_TRY(hipFree(s.tvs)); s.tvs = nullptr; }
         ps_release(i);
         if (s.keys2_ready) { if (s.bk2_ntt) HIP_TRY(hipFree(s.bk2_ntt)); HIP_TRY(hipFree(s.bk2q_ntt)); HIP_TRY(hipFree(s.ksk2)); }
         if (s.tables2) HIP_TRY(hipFree(s.tables2));
@@ -1185,6 +1263,7 @@ int cufhe_amd_cleanup(void)
         s.prof = cufhe_amd_profile{};
     }
     lvl2_release_host_key();
+    g_user_count.store(0, std::memory_order_release);
     return 0;
 }
 
@@ -1324,6 +1403,48 @@ int cufhe_amd_gate_list(int device, void* stream, int level, size_t count, const
     return run_gates(device, stream, level, count, [&](size_t g) {
         return GateRef{ops[g], outs[g], in0s[g], in1s ? in1s[g] : nullptr, in2s ? in2s[g] : nullptr};
     });
+}
+
+int cufhe_amd_define_gate(const int32_t coeffs[3], uint32_t offset, const uint32_t* test_vector, int* op)
+{
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (!coeffs || !op) return fail(-1, "null pointer");
+    if (coeffs[0] == 0) return fail(-1, "user gate: c0 must not be 0");
+    if (g_param_set >= 0) return fail(-1, "user gates run on the default path only: not while \"param_set\" is active");
+    for (int i = 0; i < g_gpu_num; i++)
+        if (!g_dev[i].keys_ready) return fail(-3, "Initialize(ek) has not been called for every device");
+    const int k = g_user_count.load(std::memory_order_relaxed);
+    if (k >= kMaxUserGates) return fail(-1, "user gate table full (CUFHE_AMD_MAX_USER_GATES definitions until CleanUp)");
+    if (test_vector) {
+        // row k of every device's table, synchronously (like the key replicas); no launch reads the row before its id exists
+        for (int i = 0; i < g_gpu_num; i++) {
+            DeviceState& s = g_dev[i];
+            HIP_TRY(hipSetDevice(phys_device(i)));
+            if (!s.tvs) {
+                DevPtr<uint32_t> t;
+                HIP_TRY(t.alloc((size_t)kMaxUserGates * kN));
+                s.tvs = t.release();
+            }
+            HIP_TRY(hipMemcpy(s.tvs + (size_t)k * kN, test_vector, kN * sizeof(uint32_t), hipMemcpyHostToDevice));
+        }
+    }
+    g_user[k] = UserGate{{coeffs[0], coeffs[1], coeffs[2]}, offset, test_vector != nullptr};
+    g_user_count.store(k + 1, std::memory_order_release);
+    *op = CUFHE_AMD_USER_OP_BASE + k;
+    return 0;
+}
+
+int cufhe_amd_test_vector(const uint32_t* values, int p, uint32_t* tv)
+{
+    if (!values || !tv) return fail(-1, "null pointer");
+    if (p < 2 || p > kN / 2 || (p & (p - 1))) return fail(-1, "p must be a power of two in [2, N/2]");
+    // coefficient j lies in the box of m = round(j p / N); the top half-box (m = p) is the wrap of m = 0's lower half: -values[0]
+    const int box = kN / p;
+    for (int j = 0; j < kN; j++) {
+        const int m = (j + box / 2) / box;
+        tv[j] = m == p ? 0u - values[0] : values[m];
+    }
+    return 0;
 }
 
 int cufhe_amd_bootstrap_batch(int device, void* stream, size_t count, uint32_t* out, const uint32_t* in)

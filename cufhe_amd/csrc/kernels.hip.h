@@ -282,7 +282,7 @@ __device__ __forceinline__ void inverse_and_add(double (&A)[kRegs], uint32_t (&a
 // shape for the tail of a launch that does not fill a second round (capi.hip: launch_blind_rotate).
 __global__ __launch_bounds__(kBrThreads, 2) void blind_rotate_kernel(
     const LinDesc* __restrict__ descs, int count, const double* __restrict__ bk_ntt,
-    const NttTables* __restrict__ gt, int steps, uint32_t* __restrict__ acc_dump, int active)
+    const NttTables* __restrict__ gt, int steps, uint32_t* __restrict__ acc_dump, int active, const uint32_t* __restrict__ tvs)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     double* tabs = (double*)(smem + kBrLdsTables);
@@ -326,6 +326,11 @@ __global__ __launch_bounds__(kBrThreads, 2) void blind_rotate_kernel(
         acc0[r] = 0;
         const bool neg = (bbar != 2 * kN) && ((e < (bbar & (kN - 1))) != ((bbar >> kNbit) != 0));
         acc1[r] = neg ? 0u - kMu : kMu;
+    }
+    if (d.pad) {              // a user gate: X^bbar times its test vector instead, 16 coefficients per lane gathered once
+        const uint32_t* tv = desc_tv(tvs, d.pad);
+#pragma unroll
+        for (int r = 0; r < kRegs; r++) acc1[r] = rotated_tv_coef(tv, bbar, lane + 64 * r);
     }
     __syncthreads();          // tables staged; abar list visible (own wave only, but cheap)
     TuFwdPinned tuf;

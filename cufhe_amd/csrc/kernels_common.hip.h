@@ -45,8 +45,29 @@ struct LinDesc {
     uint32_t* out;
     int32_t ca, cb;
     uint32_t off;
-    uint32_t pad;
+    uint32_t pad;          // blind rotations: test vector, 0 = the constant mu, k > 0 = row k - 1 of the device's user table
 };
+
+// User gates (cufhe_amd_define_gate): rows of kN torus words, one per definition, in every device's table
+constexpr int kMaxUserGates = 64;
+
+// Coefficient e of the initial accumulator's b polynomial, X^bbar * TV in Z[X]/(X^N + 1): TV[e - bbar] when 0 <= e - bbar < N, the
+// negacyclic wrap with a sign otherwise.  tv == nullptr: TV = mu everywhere (RotatedTestVector, include/gatebootstrapping_gpu.cuh:29-52).
+__device__ __forceinline__ uint32_t rotated_tv_coef(const uint32_t* __restrict__ tv, uint32_t bbar, uint32_t e)
+{
+    if (!tv) {
+        const bool neg = (bbar != 2 * kN) && ((e < (bbar & (kN - 1))) != ((bbar >> kNbit) != 0));
+        return neg ? 0u - kMu : kMu;
+    }
+    const uint32_t k = (e - bbar) & (2 * kN - 1);
+    const uint32_t v = tv[k & (kN - 1)];
+    return k >= (uint32_t)kN ? 0u - v : v;
+}
+// the row a rotation's descriptor selects in `tvs` ([kMaxUserGates][kN]), nullptr for the constant mu
+__device__ __forceinline__ const uint32_t* desc_tv(const uint32_t* __restrict__ tvs, uint32_t pad)
+{
+    return pad ? tvs + (size_t)(pad - 1) * kN : nullptr;
+}
 
 // Device fault word (one uint32 per device in host-visible memory, DeviceState::fault): bits a kernel sets when it
 // detects that its own result cannot be trusted.  The host turns any set bit into status -5 (capi.hip: device_fault).

@@ -42,7 +42,7 @@ constexpr int kLlLdsBytes = kLlLdsAbar + kAbarBytes + 16;                     //
 
 __global__ __launch_bounds__(kLlThreads) void blind_rotate_ll_kernel(
     const LinDesc* __restrict__ descs, int count, const double* __restrict__ bk_ntt,
-    const Ntt512Tables* __restrict__ gt2, int steps, uint32_t* __restrict__ acc_dump);
+    const Ntt512Tables* __restrict__ gt2, int steps, uint32_t* __restrict__ acc_dump, const uint32_t* __restrict__ tvs);
 #ifndef CUFHE_AMD_LL_DECLARATIONS_ONLY
 // The first TWO stages of half h of the forward transform on one row's gadget digits, exactly, from the DECOMPOSED WORDS of the
 // coefficients: w0[r] / w1[r] hold the word of e = lane + 64 r and e + 512 with the sign mask applied, the row's digit is the signed field
@@ -74,7 +74,7 @@ __device__ __forceinline__ void ll_split_first_stages_words(double (&x)[kRegs8],
 
 __global__ __launch_bounds__(kLlThreads) void blind_rotate_ll_kernel(
     const LinDesc* __restrict__ descs, int count, const double* __restrict__ bk_ntt,
-    const Ntt512Tables* __restrict__ gt2, int steps, uint32_t* __restrict__ acc_dump)
+    const Ntt512Tables* __restrict__ gt2, int steps, uint32_t* __restrict__ acc_dump, const uint32_t* __restrict__ tvs)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int g = blockIdx.x;
@@ -100,11 +100,11 @@ __global__ __launch_bounds__(kLlThreads) void blind_rotate_ll_kernel(
     }
     for (int i = tid; i < 2 * kN; i += kLlThreads) sumL[i] = 0.0;
     __syncthreads();
-    {   // RotatedTestVector, include/gatebootstrapping_gpu.cuh:29-52
+    {   // RotatedTestVector, include/gatebootstrapping_gpu.cuh:29-52 (mu or the descriptor's user test vector)
         const uint32_t bbar = *bbar_slot;
+        const uint32_t* tv = desc_tv(tvs, d.pad);
         for (int e = tid; e < kN; e += kLlThreads) {
-            const bool neg = (bbar != 2 * kN) && (((uint32_t)e < (bbar & (kN - 1))) != ((bbar >> kNbit) != 0));
-            const uint32_t v = neg ? 0u - kMu : kMu;
+            const uint32_t v = rotated_tv_coef(tv, bbar, (uint32_t)e);
             accL[e] = 0; accL[kN + e] = 0;
             accL[2 * kN + e] = v; accL[3 * kN + e] = v;
         }
@@ -293,11 +293,11 @@ static_assert(kLl2LdsBytes <= 160 * 1024, "paired low-latency kernel does not fi
 
 __global__ __launch_bounds__(kLlThreads) void blind_rotate_ll2_kernel(
     const LinDesc* __restrict__ descs, int count, const double* __restrict__ bk_ntt,
-    const Ntt512Tables* __restrict__ gt2, int steps, uint32_t* __restrict__ acc_dump, uint32_t* fault);
+    const Ntt512Tables* __restrict__ gt2, int steps, uint32_t* __restrict__ acc_dump, uint32_t* fault, const uint32_t* __restrict__ tvs);
 #ifndef CUFHE_AMD_LL_DECLARATIONS_ONLY
 __global__ __launch_bounds__(kLlThreads) void blind_rotate_ll2_kernel(
     const LinDesc* __restrict__ descs, int count, const double* __restrict__ bk_ntt,
-    const Ntt512Tables* __restrict__ gt2, int steps, uint32_t* __restrict__ acc_dump, uint32_t* fault)
+    const Ntt512Tables* __restrict__ gt2, int steps, uint32_t* __restrict__ acc_dump, uint32_t* fault, const uint32_t* __restrict__ tvs)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
@@ -338,12 +338,12 @@ __global__ __launch_bounds__(kLlThreads) void blind_rotate_ll2_kernel(
     }
     __syncthreads();
 #pragma unroll
-    for (int x = 0; x < 2; x++) {   // RotatedTestVector, include/gatebootstrapping_gpu.cuh:29-52
+    for (int x = 0; x < 2; x++) {   // RotatedTestVector, include/gatebootstrapping_gpu.cuh:29-52 (mu or the descriptor's user test vector)
         const uint32_t bbar = *rot[x].bbar;
+        const uint32_t* tv = desc_tv(tvs, dsc[x].pad);
         for (int e = tid; e < kN; e += kLlThreads) {
-            const bool neg = (bbar != 2 * kN) && (((uint32_t)e < (bbar & (kN - 1))) != ((bbar >> kNbit) != 0));
             rot[x].acc[e] = 0;
-            rot[x].acc[kN + e] = neg ? 0u - kMu : kMu;
+            rot[x].acc[kN + e] = rotated_tv_coef(tv, bbar, (uint32_t)e);
         }
     }
     __syncthreads();

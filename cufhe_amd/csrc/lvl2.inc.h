@@ -152,7 +152,7 @@ struct Lvl2Path {
     using Mid = uint64_t;
     static constexpr int lvl0_words = kLvl0Words, mid_words = k2Words, n = kLvl0N;
     static constexpr uint64_t ks_mu = k2Mu;
-    static constexpr bool lvl1_gates = false;
+    static constexpr bool lvl1_gates = false, user_gates = false;
     DeviceState& s;
     int ready() const { return s.keys2_ready ? 0 : fail(-3, "cufhe_amd_lvl2_initialize has not been called for this device"); }
     int rotate(hipStream_t st, const RotDesc2* d, size_t count, int steps, uint64_t* dump) const { return launch_blind_rotate_lvl2(s, st, d, count, steps, dump); }

@@ -465,12 +465,16 @@ int cufhe_amd_enqueue_gate(int device, void* stream, int op, int copying, cufhe_
 {
     std::lock_guard<std::mutex> lk(g_sched_mu);
     if (int rc = check_device(device)) return rc;
-    if (op < 0 || op >= CUFHE_AMD_NUM_OPS) return fail(-1, "unknown gate op");
+    const UserGate* u = user_gate(op);     // a user gate: an ordinary gate of one, two or three operands, kind = its output level
+    if (is_user_op(op) && !u) return fail(-1, "user gate op not defined (cufhe_amd_define_gate; CleanUp drops the definitions)");
+    if (!u && (op < 0 || op >= CUFHE_AMD_NUM_OPS)) return fail(-1, "unknown gate op");
     if (!out || !in0) return fail(-1, "null ciphertext");
-    const bool three = op == CUFHE_AMD_MUX || op == CUFHE_AMD_NMUX;
-    const bool one = op == CUFHE_AMD_NOT || op == CUFHE_AMD_COPY;
+    if (u && (g_param_set >= 0 || (g_lvl0_ring == 2048 && out->level == 0)))
+        return fail(-1, "user gates run on the default path only: not with \"param_set\" active or on the N = 2048 ring (\"lvl0_ring\")");
+    const bool three = op == CUFHE_AMD_MUX || op == CUFHE_AMD_NMUX || (u && user_gate_arity(*u) == 3);
+    const bool one = op == CUFHE_AMD_NOT || op == CUFHE_AMD_COPY || (u && user_gate_arity(*u) == 1);
     if (!one && !in1) return fail(-1, "gate needs a second operand");
-    if (three && !in2) return fail(-1, "mux needs a third operand");
+    if (three && !in2) return fail(-1, u ? "user gate needs a third operand" : "mux needs a third operand");
     cufhe_amd_ctxt* ins[3] = {in0, one ? nullptr : in1, three ? in2 : nullptr};
     sched::Scheduler* S = scheduler();
     if (int rc = sched_check_ctxt(S, out)) return rc;
@@ -481,7 +485,7 @@ int cufhe_amd_enqueue_gate(int device, void* stream, int op, int copying, cufhe_
         if (c->level != out->level) return fail(-1, "operands of one gate must have the same level");
     }
     const DeviceState& ds = g_dev[device];
-    if (!ds.keys_ready && !ds.keys2_ready && g_param_set < 0 && !one) return fail(-3, "Initialize(ek) has not been called for this device");
+    if (!ds.keys_ready && !ds.keys2_ready && g_param_set < 0 && (!one || u)) return fail(-3, "Initialize(ek) has not been called for this device");
     if (int rc = S->dev(device).record_gate(stream, op, copying != 0, out, ins)) return sched_error(S->dev(device), rc);
     return 0;
 }

@@ -118,6 +118,30 @@ int cufhe_amd_gate_list(int device, void* stream, int level, size_t count, const
                         uint32_t* const* outs, const uint32_t* const* in0s,
                         const uint32_t* const* in1s, const uint32_t* const* in2s);
 
+/* ---- user gates: programmable bootstrapping (no counterpart in the reference) ----
+ * A user gate is defined once after cufhe_amd_initialize; its op id is then accepted wherever a built-in op is: cufhe_amd_gate,
+ * _gate_batch, _gate_list and _enqueue_gate (mixed freely with built-in ops).  Definition: integer coefficients (c0, c1, c2), c0 != 0,
+ * a torus offset and an optional test vector TV of N = 1024 lvl1 torus words (NULL: the constant mu).  With
+ *     x = c0 in0 + c1 in1 + c2 in2 + (0, ..., 0, offset)   mod 2^32, at the level of the op,
+ * the gate runs the built-in two-input gate path on x -- level 0: blind rotate, SampleExtract(0), key switch; level 1: key switch,
+ * blind rotate, SampleExtract(0) -- except that the accumulator starts as (0, X^bbar TV) (negacyclic; bbar = 2N - (b >> (32 - 1 - nbit))
+ * as for the built-in gates) instead of (0, X^bbar mu).  So (ca, cb, 0) and offset of a built-in two-input gate with TV NULL, or an
+ * all-mu TV, give that gate's words exactly.  Operands: in0 only when c1 = c2 = 0, in0 and in1 when c2 = 0, else all three (c0 in0 +
+ * c1 in1 is formed first, into a temporary).
+ * Op ids: CUFHE_AMD_USER_OP_BASE + k for the k-th definition since the last cufhe_amd_cleanup, k < CUFHE_AMD_MAX_USER_GATES; the
+ * range overlaps neither enum cufhe_amd_op nor enum cufhe_amd_trlwe_op.  Definitions are immutable; the test vector is copied into
+ * every device's table before the call returns.  cufhe_amd_cleanup drops every definition: its id is refused afterwards.
+ * Refused: c0 = 0 (-1); a full table (-1); a definition while "param_set" is active (-1); before cufhe_amd_initialize (-3).  The
+ * parameter-set kernels ("param_set") and the N = 2048 ring ("lvl0_ring" 2048) have no user gates: a user op there returns -1 before
+ * any device work, as does an op id in the range that is not defined. */
+#define CUFHE_AMD_USER_OP_BASE 1000
+#define CUFHE_AMD_MAX_USER_GATES 64
+int cufhe_amd_define_gate(const int32_t coeffs[3], uint32_t offset, const uint32_t* test_vector, int* op);
+/* Host helper: the test vector (N words) of a function on a message space of p values, p a power of two, 2 <= p <= N/2, messages
+ * encoded with a padding bit as m -> m 2^32 / (2p).  Coefficient j in the box [m N/p - N/(2p), m N/p + N/(2p)) holds values[m]; the
+ * top half-box [N - N/(2p), N) holds -values[0], so that m = 0 with negative noise still gives values[0].  values: p torus words. */
+int cufhe_amd_test_vector(const uint32_t* values, int p, uint32_t* tv);
+
 /* ---- the reference's per-gate API on host-visible ciphertexts ----
  * template<class P> struct Ctxt (include/cufhe_gpu.cuh:102-121): `host_words` is the
  * caller-owned tlwehost storage (n+1 or N+1 words, kept alive by the caller); the handle

@@ -345,6 +345,39 @@ CUFHE_AMD_GATE1(Copy, CUFHE_AMD_COPY)
 CUFHE_AMD_GATE3(Mux, CUFHE_AMD_MUX)
 CUFHE_AMD_GATE3(NMux, CUFHE_AMD_NMUX)
 
+// ---- user gates: programmable bootstrapping (no counterpart in the reference; cufhe_amd_define_gate, include/cufhe_amd.h) ----
+/// a defined user gate: x = c0 in0 + c1 in1 + c2 in2 + (0, .., 0, offset) bootstrapped through its test vector
+struct UserGate {
+    int op = -1;
+};
+/// Define after Initialize; tv: N = 1024 lvl1 torus words (nullptr: the constant mu).  Valid until CleanUp.
+inline UserGate DefineGate(const std::array<int32_t, 3>& coeffs, uint32_t offset, const uint32_t* tv = nullptr)
+{
+    UserGate g;
+    CUFHE_AMD_CHECK(cufhe_amd_define_gate(coeffs.data(), offset, tv, &g.op));
+    return g;
+}
+/// the test vector of a function on values.size() messages (a power of two, 2 .. N/2) with a padding bit, m -> m 2^32 / (2p)
+inline std::vector<uint32_t> TestVector(const std::vector<uint32_t>& values)
+{
+    std::vector<uint32_t> tv(1024);             // user gates run on the default set only: N = 1024 whatever the build selects
+    CUFHE_AMD_CHECK(cufhe_amd_test_vector(values.data(), (int)values.size(), tv.data()));
+    return tv;
+}
+/// Apply: inputs from tlwehost, result delivered to out.tlwehost (like And); gApply: device buffers only (like gAnd)
+template <class P> inline void Apply(UserGate g, Ctxt<P>& out, Ctxt<P>& in0, Stream st)
+{ CUFHE_AMD_CHECK(cufhe_amd_enqueue_gate(st.device_id(), st.raw(), g.op, 1, out.handle, in0.handle, nullptr, nullptr)); }
+template <class P> inline void gApply(UserGate g, Ctxt<P>& out, Ctxt<P>& in0, Stream st)
+{ CUFHE_AMD_CHECK(cufhe_amd_enqueue_gate(st.device_id(), st.raw(), g.op, 0, out.handle, in0.handle, nullptr, nullptr)); }
+template <class P> inline void Apply(UserGate g, Ctxt<P>& out, Ctxt<P>& in0, Ctxt<P>& in1, Stream st)
+{ CUFHE_AMD_CHECK(cufhe_amd_enqueue_gate(st.device_id(), st.raw(), g.op, 1, out.handle, in0.handle, in1.handle, nullptr)); }
+template <class P> inline void gApply(UserGate g, Ctxt<P>& out, Ctxt<P>& in0, Ctxt<P>& in1, Stream st)
+{ CUFHE_AMD_CHECK(cufhe_amd_enqueue_gate(st.device_id(), st.raw(), g.op, 0, out.handle, in0.handle, in1.handle, nullptr)); }
+template <class P> inline void Apply(UserGate g, Ctxt<P>& out, Ctxt<P>& in0, Ctxt<P>& in1, Ctxt<P>& in2, Stream st)
+{ CUFHE_AMD_CHECK(cufhe_amd_enqueue_gate(st.device_id(), st.raw(), g.op, 1, out.handle, in0.handle, in1.handle, in2.handle)); }
+template <class P> inline void gApply(UserGate g, Ctxt<P>& out, Ctxt<P>& in0, Ctxt<P>& in1, Ctxt<P>& in2, Stream st)
+{ CUFHE_AMD_CHECK(cufhe_amd_enqueue_gate(st.device_id(), st.raw(), g.op, 0, out.handle, in0.handle, in1.handle, in2.handle)); }
+
 // ---- TRLWE-level primitives, include/cufhe_gpu.cuh:123-146,209-216,282-285 ----
 // Same names and operands as the reference.  GateBootstrappingTLWE2TRLWElvl01NTT, Refresh,
 // SampleExtractAndKeySwitch and CMUXNTT (and their g-forms) are RECORDED like gates and launched in batches: as in the
