@@ -95,6 +95,10 @@ SIGNATURES = {
                                            c_void, c_void, c_void, c_void]),
     "cufhe_amd_define_gate": (ctypes.c_int, [c_i32p, ctypes.c_uint32, c_u32p, ctypes.POINTER(ctypes.c_int)]),
     "cufhe_amd_test_vector": (ctypes.c_int, [c_u32p, ctypes.c_int, c_u32p]),
+    "cufhe_amd_define_gate_multi": (ctypes.c_int, [c_i32p, ctypes.c_uint32, ctypes.c_int, c_u32p, ctypes.POINTER(ctypes.c_int)]),
+    "cufhe_amd_test_vector_multi": (ctypes.c_int, [c_u32p, ctypes.c_int, ctypes.c_int, c_u32p]),
+    "cufhe_amd_enqueue_gate_multi": (ctypes.c_int, [ctypes.c_int, c_void, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void, c_void, c_void,
+                                                    c_void]),
     "cufhe_amd_ctxt_create": (ctypes.c_int, [ctypes.c_int, c_void, ctypes.POINTER(c_void)]),
     "cufhe_amd_ctxt_destroy": (ctypes.c_int, [c_void]),
     "cufhe_amd_ctxt_device_ptr": (c_void, [c_void, ctypes.c_int]),

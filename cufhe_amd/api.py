@@ -286,9 +286,11 @@ NMux, gNMux = _make3(NMUX, True), _make3(NMUX, False)
 USER_OP_BASE, MAX_USER_GATES = 1000, 64
 
 
-def define_gate(coeffs, offset=0, test_vector=None):
+def define_gate(coeffs, offset=0, test_vector=None, nout=1):
     """A user gate x = c0 in0 + c1 in1 + c2 in2 + (0, .., 0, offset) bootstrapped through `test_vector` (N torus words; None: the
-    constant mu).  coeffs: one to three integers (missing ones are 0).  Returns the op id, usable wherever a built-in op is."""
+    constant mu).  coeffs: one to three integers (missing ones are 0).  Returns the op id, usable wherever a built-in op is.
+    nout = 2, 4 or 8: a multi-output gate (cufhe_amd_define_gate_multi; test_vector from test_vector_multi, required); output j is
+    user_op_output(op, j)."""
     c = np.zeros(3, dtype=np.int32)
     c[:len(coeffs)] = coeffs
     tv = None
@@ -296,10 +298,32 @@ def define_gate(coeffs, offset=0, test_vector=None):
         tv = np.ascontiguousarray(test_vector, dtype=np.uint32)
         if tv.size != PARAMS.N:
             raise ValueError(f"test vector must have N = {PARAMS.N} words")
+    tvp = tv.ctypes.data_as(_lib.c_u32p) if tv is not None else None
     op = ctypes.c_int()
-    check(lib.cufhe_amd_define_gate(c.ctypes.data_as(_lib.c_i32p), int(offset) & 0xFFFFFFFF,
-                                    tv.ctypes.data_as(_lib.c_u32p) if tv is not None else None, ctypes.byref(op)))
+    if nout == 1:
+        check(lib.cufhe_amd_define_gate(c.ctypes.data_as(_lib.c_i32p), int(offset) & 0xFFFFFFFF, tvp, ctypes.byref(op)))
+    else:
+        check(lib.cufhe_amd_define_gate_multi(c.ctypes.data_as(_lib.c_i32p), int(offset) & 0xFFFFFFFF, int(nout), tvp, ctypes.byref(op)))
     return op.value
+
+
+def user_op_output(op, j):
+    """The op id of output j of multi-output definition `op` (CUFHE_AMD_USER_OP_OUTPUT)."""
+    return op + j * MAX_USER_GATES
+
+
+def test_vector_multi(values):
+    """The interleaved test vector of nout functions on p messages: values is [nout][p] torus words (cufhe_amd_test_vector_multi);
+    TV[nout q + j] = values[j][box of position nout q]."""
+    v = np.ascontiguousarray(values, dtype=np.uint32)
+    if v.ndim != 2:
+        raise ValueError("values must be [nout][p]")
+    tv = np.empty(PARAMS.N, dtype=np.uint32)
+    check(lib.cufhe_amd_test_vector_multi(v.ctypes.data_as(_lib.c_u32p), int(v.shape[1]), int(v.shape[0]), tv.ctypes.data_as(_lib.c_u32p)))
+    return tv
+
+
+test_vector_multi.__test__ = False
 
 
 def test_vector(values):
@@ -325,6 +349,25 @@ def gApply(op, out, *ins_and_st):
     """gApply(op, out, in0[, in1[, in2]], st): the device-resident form, like gAnd(..)."""
     *ins, st = ins_and_st
     _gate(op, False, out, ins, st)
+
+
+def _gate_multi(op, copying, outs, ins, st):
+    hs = [c._h for c in ins] + [None] * (3 - len(ins))
+    arr = (ctypes.c_void_p * len(outs))(*[o._h for o in outs])
+    check(lib.cufhe_amd_enqueue_gate_multi(st.device_id(), st.st(), op, 1 if copying else 0, len(outs), arr, *hs))
+
+
+def ApplyMulti(op, outs, *ins_and_st):
+    """ApplyMulti(op, [o0, o1, ..], in0[, in1[, in2]], st): all outputs of one evaluation of a multi-output gate (one rotation), inputs
+    from tlwehost, results delivered to each output's tlwehost."""
+    *ins, st = ins_and_st
+    _gate_multi(op, True, list(outs), ins, st)
+
+
+def gApplyMulti(op, outs, *ins_and_st):
+    """gApplyMulti(op, [o0, o1, ..], in0[, in1[, in2]], st): the device-resident form."""
+    *ins, st = ins_and_st
+    _gate_multi(op, False, list(outs), ins, st)
 
 
 # ---- native batched entry points (what bench.py and the parity tests drive) ----

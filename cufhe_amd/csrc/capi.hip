@@ -719,17 +719,33 @@ using sched::GateRef;
 // User gates (cufhe_amd_define_gate): definition k is op CUFHE_AMD_USER_OP_BASE + k.  A definition is written once, before
 // g_user_count is raised past it, and never changes afterwards, so the gate paths read it without a lock; its test vector is row k
 // of every device's DeviceState::tvs.  CleanUp drops them all.
-struct UserGate { int32_t c[3]; uint32_t off; bool tv; };
+// A multi-output definition (cufhe_amd_define_gate_multi) has nout = 2^s > 1 outputs: output j of definition k is op
+// CUFHE_AMD_USER_OP_OUTPUT(base + k, j) = base + k + j * CUFHE_AMD_MAX_USER_GATES, and its rotations carry s beside the row
+// (make_pad).  A single-output definition has nout = 1, s = 0.
+struct UserGate { int32_t c[3]; uint32_t off; bool tv; int nout; int s; };
 static_assert(CUFHE_AMD_MAX_USER_GATES == kMaxUserGates, "the header's capacity is the device table's");
 static_assert(CUFHE_AMD_USER_OP_BASE > CUFHE_AMD_TL_CMUX, "user op ids do not overlap the built-in or TRLWE-level ops");
+static_assert(CUFHE_AMD_USER_OP_OUTPUT(CUFHE_AMD_USER_OP_BASE + kMaxUserGates - 1, (1 << kMaxOutputShift) - 1) ==
+                  CUFHE_AMD_USER_OP_BASE + (kMaxUserGates << kMaxOutputShift) - 1, "output ids fill [base, base + 8 * 64)");
 UserGate g_user[kMaxUserGates];
 std::atomic<int> g_user_count{0};
-bool is_user_op(int op) { return op >= CUFHE_AMD_USER_OP_BASE && op < CUFHE_AMD_USER_OP_BASE + kMaxUserGates; }
-// the definition of `op`; nullptr when op is not a defined user gate
+bool is_user_op(int op) { return op >= CUFHE_AMD_USER_OP_BASE && op < CUFHE_AMD_USER_OP_BASE + (kMaxUserGates << kMaxOutputShift); }
+int user_def(int op) { return (op - CUFHE_AMD_USER_OP_BASE) % kMaxUserGates; }      // definition index k of a user op id
+int user_output(int op) { return (op - CUFHE_AMD_USER_OP_BASE) / kMaxUserGates; }   // output j of a user op id
+// the definition of `op`; nullptr when op is not a defined user gate or names an output j >= nout of one
 const UserGate* user_gate(int op)
 {
-    const int k = op - CUFHE_AMD_USER_OP_BASE;
-    return k >= 0 && k < g_user_count.load(std::memory_order_acquire) ? &g_user[k] : nullptr;
+    if (!is_user_op(op)) return nullptr;
+    const int k = user_def(op);
+    if (k >= g_user_count.load(std::memory_order_acquire)) return nullptr;
+    return user_output(op) < g_user[k].nout ? &g_user[k] : nullptr;
+}
+// the refusal of a user op id that names no defined gate: an undefined definition, or an output id (j > 0) that no multi-output
+// definition has
+int fail_user_op(int op)
+{
+    if (user_output(op) == 0) return fail(-1, "user gate op not defined (cufhe_amd_define_gate; CleanUp drops the definitions)");
+    return fail(-1, "unknown gate op: not an output of a defined multi-output user gate (CUFHE_AMD_USER_OP_OUTPUT(op, j), j < nout)");
 }
 // operands a user gate reads: in0 (c1 = c2 = 0), in0 and in1 (c2 = 0), all three
 int user_gate_arity(const UserGate& u) { return u.c[2] ? 3 : u.c[1] ? 2 : 1; }
@@ -778,13 +794,35 @@ int lower_gates(const P& p, hipStream_t st, int level, size_t count, GetGate get
     if (count == 0) return 0;
     const uint32_t negmu = 0u - kMu;
 
+    // Outputs of one multi-output definition on the same operands form one evaluation (one rotation, all nout outputs extracted into
+    // scratch): fused by (definition, in0, in1, in2) whatever the order of the list.  fuse[g] is the evaluation of gate g.
+    struct Eval { uint32_t* t1; uint32_t* t0; bool done; };
+    std::map<std::tuple<int, const uint32_t*, const uint32_t*, const uint32_t*>, size_t> evals;
+    std::vector<size_t> fuse;
+    std::vector<Eval> ev;
+    size_t nmulti_words = 0;
     // first pass: count temporaries
     size_t nrot = 0, npre = 0;
     for (size_t g = 0; g < count; g++) {
         const int op = get(g).op;
         if (is_user_op(op)) {
             const UserGate* u = user_gate(op);
-            if (!u) return fail(-1, "user gate op not defined (cufhe_amd_define_gate; CleanUp drops the definitions)");
+            if (!u) return fail_user_op(op);
+            if (u->nout > 1) {
+                const GateRef gr = get(g);
+                const int arity = user_gate_arity(*u);
+                const auto key = std::make_tuple(user_def(op), (const uint32_t*)gr.in0, arity >= 2 ? gr.in1 : nullptr, arity == 3 ? gr.in2 : nullptr);
+                if (fuse.empty()) fuse.assign(count, (size_t)-1);
+                auto it = evals.find(key);
+                if (it == evals.end()) {
+                    it = evals.emplace(key, ev.size()).first;
+                    ev.push_back({nullptr, nullptr, false});
+                    nmulti_words += (size_t)u->nout;
+                    if (arity == 3) npre += 1;
+                }
+                fuse[g] = it->second;
+                continue;
+            }
             nrot += 1;
             if (user_gate_arity(*u) == 3) npre += 1;
             continue;
@@ -798,8 +836,15 @@ int lower_gates(const P& p, hipStream_t st, int level, size_t count, GetGate get
     {
         const size_t desc = std::max({sizeof(typename P::RotD), sizeof(typename P::KsD), sizeof(LinDesc)});
         const size_t need = nrot * (P::mid_words * sizeof(Mid) + P::lvl0_words * sizeof(uint32_t)) + npre * level_words * sizeof(uint32_t) +
-                            (count * 6 + 8) * desc + 8192;
+                            nmulti_words * P::mid_words * sizeof(Mid) + ev.size() * P::lvl0_words * sizeof(uint32_t) + (count * 6 + 8) * desc + 8192;
         if (int rc = open_scratch(p.s, st, need, &sc)) return rc;
+    }
+    Mid* tmpm = nullptr;          // the multi-output evaluations' outputs, nout contiguous lvl1 ciphertexts each
+    uint32_t* tmpm0 = nullptr;    // level 1: their key switches' results, one per evaluation
+    if (!ev.empty()) {
+        if (int rc = sc.alloc((void**)&tmpm, nmulti_words * P::mid_words * sizeof(Mid))) return rc;
+        if (level == 1)
+            if (int rc = sc.alloc((void**)&tmpm0, ev.size() * P::lvl0_words * sizeof(uint32_t))) return rc;
     }
     Mid* tmp1 = nullptr;          // the rotations' results, one per rotation
     uint32_t* tmp0 = nullptr;     // level 1: the key switches' results, one per rotation
@@ -815,11 +860,44 @@ int lower_gates(const P& p, hipStream_t st, int level, size_t count, GetGate get
     std::vector<typename P::KsD> ks;
     std::vector<LinDesc> lin, pre;
     rot.reserve(count * 2); ks.reserve(count * 2); lin.reserve(count); pre.reserve(npre);
-    size_t ir = 0;
+    size_t ir = 0, im = 0;
     for (size_t g = 0; g < count; g++) {
         const GateRef gr = get(g);
         if (!gr.out || !gr.in0) return fail(-1, "null ciphertext pointer");
         if constexpr (P::user_gates) {
+            if (const UserGate* u = user_gate(gr.op); u && u->nout > 1) {
+                // output j of a multi-output evaluation: the evaluation's one rotation is emitted with its first requested output;
+                // level 0: the key switch of scratch output j into out; level 1: a copy of scratch output j into out (last lincomb)
+                const int arity = user_gate_arity(*u);
+                if (arity >= 2 && !gr.in1) return fail(-1, "user gate needs a second operand");
+                if (arity == 3 && !gr.in2) return fail(-1, "user gate needs a third operand");
+                Eval& e = ev[fuse[g]];
+                if (!e.done) {
+                    e.done = true;
+                    e.t1 = (uint32_t*)(tmpm + im * P::mid_words);
+                    im += (size_t)u->nout;
+                    const uint32_t* a = gr.in0;
+                    const uint32_t* b = arity >= 2 ? gr.in1 : gr.in0;
+                    int32_t ca = u->c[0], cb = u->c[1];
+                    if (arity == 3) {
+                        uint32_t* t = tmpp + pre.size() * level_words;
+                        pre.push_back({gr.in0, gr.in1, t, u->c[0], u->c[1], 0u, 0u});
+                        a = t; b = gr.in2; ca = 1; cb = u->c[2];
+                    }
+                    const uint32_t pad = make_pad(user_def(gr.op), u->s);
+                    if (level == 0) {
+                        rot.push_back({a, b, (Mid*)e.t1, ca, cb, u->off, pad});
+                    } else {
+                        e.t0 = tmpm0 + fuse[g] * P::lvl0_words;
+                        ks.push_back({a, b, e.t0, ca, cb, u->off});
+                        rot.push_back({e.t0, e.t0, (Mid*)e.t1, 1, 0, 0u, pad});
+                    }
+                }
+                Mid* tj = (Mid*)e.t1 + (size_t)user_output(gr.op) * P::mid_words;
+                if (level == 0) ks.push_back({tj, tj, gr.out, 1, 0, 0u});
+                else lin.push_back({(const uint32_t*)tj, (const uint32_t*)tj, (uint32_t*)gr.out, 1, 0, 0u, 0u});
+                continue;
+            }
             if (const UserGate* u = user_gate(gr.op)) {
                 // x = c0 in0 + c1 in1 + c2 in2 + (0, ..., 0, off) through the two-input gate path; the rotation starts from the
                 // definition's test vector (LinDesc::pad = row + 1) or from mu (pad 0)
@@ -1024,7 +1102,7 @@ int run_gates(int device, void* stream, int level, size_t count, GetGate get)
     for (size_t g = 0; g < count; g++) {
         const int op = get(g).op;
         if (!is_user_op(op)) continue;
-        if (!user_gate(op)) return fail(-1, "user gate op not defined (cufhe_amd_define_gate; CleanUp drops the definitions)");
+        if (!user_gate(op)) return fail_user_op(op);
         if (!user_ok) return fail(-1, "user gates run on the default path only: not with \"param_set\" active or on the N = 2048 ring (\"lvl0_ring\")");
     }
     if (level == 0 && g_lvl0_ring == 2048) return run_gates_lvl2(device, stream, count, get);
@@ -1405,9 +1483,9 @@ int cufhe_amd_gate_list(int device, void* stream, int level, size_t count, const
     });
 }
 
-int cufhe_amd_define_gate(const int32_t coeffs[3], uint32_t offset, const uint32_t* test_vector, int* op)
+// definition k = g_user_count of a user gate with nout = 2^s outputs (1: cufhe_amd_define_gate); the caller holds g_mu
+int define_user_gate(const int32_t coeffs[3], uint32_t offset, const uint32_t* test_vector, int s, int* op)
 {
-    std::lock_guard<std::mutex> lk(g_mu);
     if (!coeffs || !op) return fail(-1, "null pointer");
     if (coeffs[0] == 0) return fail(-1, "user gate: c0 must not be 0");
     if (g_param_set >= 0) return fail(-1, "user gates run on the default path only: not while \"param_set\" is active");
@@ -1428,10 +1506,24 @@ int cufhe_amd_define_gate(const int32_t coeffs[3], uint32_t offset, const uint32
             HIP_TRY(hipMemcpy(s.tvs + (size_t)k * kN, test_vector, kN * sizeof(uint32_t), hipMemcpyHostToDevice));
         }
     }
-    g_user[k] = UserGate{{coeffs[0], coeffs[1], coeffs[2]}, offset, test_vector != nullptr};
+    g_user[k] = UserGate{{coeffs[0], coeffs[1], coeffs[2]}, offset, test_vector != nullptr, 1 << s, s};
     g_user_count.store(k + 1, std::memory_order_release);
     *op = CUFHE_AMD_USER_OP_BASE + k;
     return 0;
+}
+
+int cufhe_amd_define_gate(const int32_t coeffs[3], uint32_t offset, const uint32_t* test_vector, int* op)
+{
+    std::lock_guard<std::mutex> lk(g_mu);
+    return define_user_gate(coeffs, offset, test_vector, 0, op);
+}
+
+int cufhe_amd_define_gate_multi(const int32_t coeffs[3], uint32_t offset, int nout, const uint32_t* test_vector, int* op)
+{
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (nout != 2 && nout != 4 && nout != 8) return fail(-1, "multi-output user gate: nout must be 2, 4 or 8");
+    if (!test_vector) return fail(-1, "multi-output user gate: the test vector is required");
+    return define_user_gate(coeffs, offset, test_vector, nout == 2 ? 1 : nout == 4 ? 2 : 3, op);
 }
 
 int cufhe_amd_test_vector(const uint32_t* values, int p, uint32_t* tv)
@@ -1443,6 +1535,23 @@ int cufhe_amd_test_vector(const uint32_t* values, int p, uint32_t* tv)
     for (int j = 0; j < kN; j++) {
         const int m = (j + box / 2) / box;
         tv[j] = m == p ? 0u - values[0] : values[m];
+    }
+    return 0;
+}
+
+int cufhe_amd_test_vector_multi(const uint32_t* values, int p, int nout, uint32_t* tv)
+{
+    if (!values || !tv) return fail(-1, "null pointer");
+    if (nout != 1 && nout != 2 && nout != 4 && nout != 8) return fail(-1, "nout must be 1, 2, 4 or 8");
+    if (p < 2 || (p & (p - 1)) || p * nout > kN / 2) return fail(-1, "p must be a power of two >= 2 with p nout <= N/2");
+    // TV[nout q + j] = values[j][m], m the box of position nout q under cufhe_amd_test_vector's boxes (the top half-box: -values[j][0])
+    const int box = kN / p;
+    for (int q = 0; q < kN / nout; q++) {
+        const int m = (nout * q + box / 2) / box;
+        for (int j = 0; j < nout; j++) {
+            const uint32_t* v = values + (size_t)j * p;
+            tv[nout * q + j] = m == p ? 0u - v[0] : v[m];
+        }
     }
     return 0;
 }

@@ -329,8 +329,14 @@ __global__ __launch_bounds__(kBrThreads, 2) void blind_rotate_kernel(
     }
     if (d.pad) {              // a user gate: X^bbar times its test vector instead, 16 coefficients per lane gathered once
         const uint32_t* tv = desc_tv(tvs, d.pad);
+        const int s = desc_shift(d.pad);
+        uint32_t bb = bbar;
+        if (s) {              // multi-output: the modulus switch again, rounded to multiples of 2^s (abar list and bbar overwritten)
+            for (int i = lane; i < kLvl0N; i += 64) abar_lds[i] = (uint16_t)ms_abar((uint32_t)d.ca * d.in0[i] + (uint32_t)d.cb * d.in1[i], s);
+            bb = ms_bbar(bword, s);
+        }
 #pragma unroll
-        for (int r = 0; r < kRegs; r++) acc1[r] = rotated_tv_coef(tv, bbar, lane + 64 * r);
+        for (int r = 0; r < kRegs; r++) acc1[r] = rotated_tv_coef(tv, bb, lane + 64 * r);
     }
     __syncthreads();          // tables staged; abar list visible (own wave only, but cheap)
     TuFwdPinned tuf;
@@ -378,6 +384,10 @@ __global__ __launch_bounds__(kBrThreads, 2) void blind_rotate_kernel(
             const int e = lane + 64 * r;
             if (e == 0) { o[0] = acc0[r]; o[kN] = acc1[r]; }
             else o[kN - e] = 0u - acc0[r];
+        }
+        if (const int s = desc_shift(d.pad)) {      // multi-output: SampleExtract(j), j = 1 .. 2^s - 1, behind output 0
+#pragma unroll
+            for (int r = 0; r < kRegs; r++) extract_more(o, 1 << s, lane + 64 * r, acc0[r], acc1[r]);
         }
     }
 }

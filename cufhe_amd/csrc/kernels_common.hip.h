@@ -45,7 +45,8 @@ struct LinDesc {
     uint32_t* out;
     int32_t ca, cb;
     uint32_t off;
-    uint32_t pad;          // blind rotations: test vector, 0 = the constant mu, k > 0 = row k - 1 of the device's user table
+    uint32_t pad;          // blind rotations: test vector, 0 = the constant mu, else row (pad & 0xff) - 1 of the device's user table and
+                           // s = pad >> 8 (desc_shift): 2^s outputs of one rotation (multi-output user gates; 0 for every other rotation)
 };
 
 // User gates (cufhe_amd_define_gate): rows of kN torus words, one per definition, in every device's table
@@ -66,7 +67,30 @@ __device__ __forceinline__ uint32_t rotated_tv_coef(const uint32_t* __restrict__
 // the row a rotation's descriptor selects in `tvs` ([kMaxUserGates][kN]), nullptr for the constant mu
 __device__ __forceinline__ const uint32_t* desc_tv(const uint32_t* __restrict__ tvs, uint32_t pad)
 {
-    return pad ? tvs + (size_t)(pad - 1) * kN : nullptr;
+    return pad ? tvs + (size_t)((pad & 0xffu) - 1) * kN : nullptr;
+}
+
+// Multi-output user gates (cufhe_amd_define_gate_multi, many-LUT bootstrapping): 2^s functions interleaved in one test vector, the
+// modulus switch rounded to multiples of 2^s, outputs j = 0 .. 2^s - 1 extracted at index j of the one rotated accumulator.
+constexpr int kMaxOutputShift = 3;                       // at most 8 outputs
+__host__ __device__ constexpr uint32_t make_pad(int row, int s) { return (uint32_t)(row + 1) | ((uint32_t)s << 8); }
+__device__ __forceinline__ int desc_shift(uint32_t pad) { return (int)(pad >> 8); }
+// abar_i = ((a_i + 2^(30 - nbit + s)) >> (31 - nbit + s)) << s and bbar = 2N - ((b >> (31 - nbit + s)) << s); s = 0 is the gates' own
+__device__ __forceinline__ uint32_t ms_abar(uint32_t a, int s) { return ((a + (1u << (32 - 2 - kNbit + s))) >> (32 - 1 - kNbit + s)) << s; }
+__device__ __forceinline__ uint32_t ms_bbar(uint32_t b, int s) { return 2 * kN - ((b >> (32 - 1 - kNbit + s)) << s); }
+// Coefficient e (a_e, b_e) of the rotated accumulator into outputs j = 1 .. nout - 1 (lvl1 TLWEs of kN + 1 words, contiguous behind
+// output 0 at `out`): SampleExtract(j) is out_j[m] = a[j - m] (m <= j), -a[N + j - m] (m > j), out_j[N] = b[j].
+__device__ __forceinline__ void extract_more(uint32_t* __restrict__ out, int nout, uint32_t e, uint32_t a, uint32_t b)
+{
+    for (int j = 1; j < nout; j++) {
+        uint32_t* o = out + (size_t)j * (kN + 1);
+        if (e <= (uint32_t)j) {
+            o[j - e] = a;
+            if (e == (uint32_t)j) o[kN] = b;
+        } else {
+            o[kN + j - e] = 0u - a;
+        }
+    }
 }
 
 // Device fault word (one uint32 per device in host-visible memory, DeviceState::fault): bits a kernel sets when it

@@ -98,6 +98,13 @@ __global__ __launch_bounds__(kLlThreads) void blind_rotate_ll_kernel(
         if (i < kLvl0N) abar_lds[i] = (uint16_t)((c + (1u << (32 - 2 - kNbit))) >> (32 - 1 - kNbit));
         else *bbar_slot = 2 * kN - ((c + d.off) >> (32 - 1 - kNbit));
     }
+    if (const int s = desc_shift(d.pad)) {      // multi-output: the same words rounded to multiples of 2^s (each thread its own slots)
+        for (int i = tid; i <= kLvl0N; i += kLlThreads) {
+            const uint32_t c = (uint32_t)d.ca * d.in0[i] + (uint32_t)d.cb * d.in1[i];
+            if (i < kLvl0N) abar_lds[i] = (uint16_t)ms_abar(c, s);
+            else *bbar_slot = ms_bbar(c + d.off, s);
+        }
+    }
     for (int i = tid; i < 2 * kN; i += kLlThreads) sumL[i] = 0.0;
     __syncthreads();
     {   // RotatedTestVector, include/gatebootstrapping_gpu.cuh:29-52 (mu or the descriptor's user test vector)
@@ -271,6 +278,8 @@ __global__ __launch_bounds__(kLlThreads) void blind_rotate_ll_kernel(
             if (e == 0) { o[0] = accL[0]; o[kN] = accL[2 * kN]; }
             else o[kN - e] = 0u - accL[e];
         }
+        if (const int s = desc_shift(d.pad))      // multi-output: SampleExtract(j), j = 1 .. 2^s - 1, behind output 0
+            for (int e = tid; e < kN; e += kLlThreads) extract_more(o, 1 << s, (uint32_t)e, accL[e], accL[2 * kN + e]);
     }
 }
 #endif
@@ -333,6 +342,13 @@ __global__ __launch_bounds__(kLlThreads) void blind_rotate_ll2_kernel(
             const uint32_t c = (uint32_t)dsc[x].ca * dsc[x].in0[i] + (uint32_t)dsc[x].cb * dsc[x].in1[i];
             if (i < kLvl0N) rot[x].abar[i] = (uint16_t)((c + (1u << (32 - 2 - kNbit))) >> (32 - 1 - kNbit));
             else *rot[x].bbar = 2 * kN - ((c + dsc[x].off) >> (32 - 1 - kNbit));
+        }
+        if (const int s = desc_shift(dsc[x].pad)) {      // multi-output: the same words rounded to multiples of 2^s
+            for (int i = tid; i <= kLvl0N; i += kLlThreads) {
+                const uint32_t c = (uint32_t)dsc[x].ca * dsc[x].in0[i] + (uint32_t)dsc[x].cb * dsc[x].in1[i];
+                if (i < kLvl0N) rot[x].abar[i] = (uint16_t)ms_abar(c, s);
+                else *rot[x].bbar = ms_bbar(c + dsc[x].off, s);
+            }
         }
         for (int i = tid; i < 2 * kN; i += kLlThreads) rot[x].sum[i] = 0.0;
     }
@@ -543,6 +559,8 @@ __global__ __launch_bounds__(kLlThreads) void blind_rotate_ll2_kernel(
                 if (e == 0) { o[0] = rot[x].acc[0]; o[kN] = rot[x].acc[kN]; }
                 else o[kN - e] = 0u - rot[x].acc[e];
             }
+            if (const int s = desc_shift(dsc[x].pad))      // multi-output: SampleExtract(j), j = 1 .. 2^s - 1, behind output 0
+                for (int e = tid; e < kN; e += kLlThreads) extract_more(o, 1 << s, (uint32_t)e, rot[x].acc[e], rot[x].acc[kN + e]);
         }
     }
 }

@@ -118,6 +118,9 @@ class Backend {
     virtual bool lane_model(LaneModel* /*m*/) { return false; }
     virtual double launch_ms(size_t /*n*/) { return 0.0; }
     virtual int gate_weight(int /*op*/) { return 1; }
+    // whether `op` is an output of a multi-output gate (several outputs of one evaluation share its rotation only when they sit in one
+    // run_gates call): a flush that holds one is left to the level order, which keeps them together (compile_two_lane)
+    virtual bool shares_rotation(int /*op*/) { return false; }
     // the same as run_gates with the launch shape of a lane: 0 = chain, 1 = bulk (anything else: by the backend's own rules)
     virtual int run_gates_lane(int s, int level, const GateRef* g, size_t n, int /*lane*/) { return run_gates(s, level, g, n); }
     virtual int caller_stream_wait(void* /*caller_stream*/, void* /*ev*/) { return 0; }
@@ -432,6 +435,11 @@ class DeviceSched {
 
     // kind: which launch group the gate joins (the output's level for ordinary gates, 2 for TRLWE-level operations)
     int record_gate(void* stream, int op, bool copying, cufhe_amd_ctxt* out, cufhe_amd_ctxt* const (&ins)[3], int kind = -1);
+    // The n outputs of ONE evaluation (a multi-output user gate): ops[j] writes outs[j], all from the same operands.  They are
+    // recorded in one dependence level -- the latest any of them needs -- with no flush between them, so that the level's run_gates
+    // call holds all of them and the backend evaluates them once.  The caller has checked that no output is an input and that the
+    // outputs are distinct handles.
+    int record_gate_group(void* stream, const int* ops, bool copying, cufhe_amd_ctxt* const* outs, size_t n, cufhe_amd_ctxt* const (&ins)[3]);
     int record_copy(void* stream, cufhe_amd_ctxt* c, bool to_device);
     int flush(size_t max_levels = (size_t)-1);
     int flush_for_completion()                 // the caller is about to wait for everything: renamed values go home in the same flush
@@ -742,6 +750,8 @@ class DeviceSched {
     void* cached_stream_ = nullptr;
     StreamState* cached_ss_ = nullptr;
     std::vector<Plan*> plan_pool_;              // retired levels, vectors keep their capacity
+    uint32_t group_floor_ = 0;                  // record_gate_group: the level all outputs of the evaluation take
+    bool hold_flush_ = false;                   // record_gate_group: no flush between the outputs of one evaluation
     uint64_t next_group_ = 1;
     std::deque<Group*> live_;                   // launched or queued groups, oldest first
     int sticky_error_ = 0;
@@ -1036,6 +1046,30 @@ inline void DeviceSched::record_upload(cufhe_amd_ctxt* c, void* stream)
     stats_.uploads++;
 }
 
+inline int DeviceSched::record_gate_group(void* stream, const int* ops, bool copying, cufhe_amd_ctxt* const* outs, size_t n,
+                                          cufhe_amd_ctxt* const (&ins)[3])
+{
+    // the level each output would take on its own (record_gate below: an output with recorded users is renamed when renaming is on)
+    uint32_t Din = base_depth_;
+    for (int i = 0; i < 3; i++)
+        if (ins[i]) Din = std::max(Din, ins[i]->d[device_].ready);
+    uint32_t floor = Din;
+    for (size_t j = 0; j < n; j++) {
+        const cufhe_amd_ctxt::PerDev& po = outs[j]->d[device_];
+        uint32_t D = std::max(Din, po.ready);
+        if (has_readers(po)) D = std::max(D, max_reader(po) + 1);
+        if (!(rename_outputs && outs[j]->level <= 1)) floor = std::max(floor, D);
+    }
+    group_floor_ = floor;
+    hold_flush_ = true;
+    int rc = 0;
+    for (size_t j = 0; j < n && !rc; j++) rc = record_gate(stream, ops[j], copying, outs[j], ins);
+    group_floor_ = 0;
+    hold_flush_ = false;
+    if (rc) return rc;
+    return after_record();
+}
+
 inline int DeviceSched::record_gate(void* stream, int op, bool copying, cufhe_amd_ctxt* out,
                                     cufhe_amd_ctxt* const (&ins)[3], int kind)
 {
@@ -1101,6 +1135,7 @@ inline int DeviceSched::record_gate(void* stream, int op, bool copying, cufhe_am
     } else if (D > Din || users) {
         hazard_by_level = true;
     }
+    D = std::max(D, group_floor_);     // record_gate_group: every output of the evaluation in one level
 
     Plan& p = plan_at(D);
     if (hazard_by_level) p.level_ordered = true;
@@ -1172,7 +1207,7 @@ inline int DeviceSched::record_gate(void* stream, int op, bool copying, cufhe_am
     note_stream(p, stream, D);
     pending_gates_++;
     stats_.gates++;
-    return after_record();
+    return hold_flush_ ? 0 : after_record();
 }
 
 inline int DeviceSched::record_copy(void* stream, cufhe_amd_ctxt* c, bool to_device)
@@ -1419,6 +1454,7 @@ inline bool DeviceSched::compile_two_lane(Group* g, TwoLanePlan* out)
         for (size_t gi = 0; gi < n; gi++) {
             const size_t id = off[pi] + gi;
             gref[id] = &p->gates[kind][gi];
+            if (be_->shares_rotation(p->gates[kind][gi].op)) return false;     // sibling outputs: one rotation in the level order only
             weight[id] = (uint8_t)std::max(0, std::min(255, be_->gate_weight(p->gates[kind][gi].op)));
             rotations += weight[id];
             const GateDep& d = p->deps[kind][gi];

@@ -165,6 +165,11 @@ class HipBackend : public sched::Backend {
         return (double)full * 18.25 + (tail ? small(tail) : 0.0);      // tools/tail_times.py, gpurun_out/r06_tail_times_ks.txt
     }
     int gate_weight(int op) override { return op == CUFHE_AMD_MUX || op == CUFHE_AMD_NMUX ? 2 : op == CUFHE_AMD_NOT || op == CUFHE_AMD_COPY ? 0 : 1; }
+    bool shares_rotation(int op) override
+    {
+        const UserGate* u = user_gate(op);
+        return u && u->nout > 1;
+    }
     int run_gates_lane(int s, int level, const sched::GateRef* g, size_t n, int lane) override
     {
         // chain lane: the paired low-latency kernel (the single one for at most a rotation per CU of its half); bulk lane: the batch kernel
@@ -466,7 +471,7 @@ int cufhe_amd_enqueue_gate(int device, void* stream, int op, int copying, cufhe_
     std::lock_guard<std::mutex> lk(g_sched_mu);
     if (int rc = check_device(device)) return rc;
     const UserGate* u = user_gate(op);     // a user gate: an ordinary gate of one, two or three operands, kind = its output level
-    if (is_user_op(op) && !u) return fail(-1, "user gate op not defined (cufhe_amd_define_gate; CleanUp drops the definitions)");
+    if (is_user_op(op) && !u) return fail_user_op(op);
     if (!u && (op < 0 || op >= CUFHE_AMD_NUM_OPS)) return fail(-1, "unknown gate op");
     if (!out || !in0) return fail(-1, "null ciphertext");
     if (u && (g_param_set >= 0 || (g_lvl0_ring == 2048 && out->level == 0)))
@@ -487,6 +492,47 @@ int cufhe_amd_enqueue_gate(int device, void* stream, int op, int copying, cufhe_
     const DeviceState& ds = g_dev[device];
     if (!ds.keys_ready && !ds.keys2_ready && g_param_set < 0 && (!one || u)) return fail(-3, "Initialize(ek) has not been called for this device");
     if (int rc = S->dev(device).record_gate(stream, op, copying != 0, out, ins)) return sched_error(S->dev(device), rc);
+    return 0;
+}
+
+int cufhe_amd_enqueue_gate_multi(int device, void* stream, int op, int copying, int nout, cufhe_amd_ctxt* const* outs,
+                                 cufhe_amd_ctxt* in0, cufhe_amd_ctxt* in1, cufhe_amd_ctxt* in2)
+{
+    std::lock_guard<std::mutex> lk(g_sched_mu);
+    if (int rc = check_device(device)) return rc;
+    const UserGate* u = user_gate(op);
+    if (is_user_op(op) && !u) return fail_user_op(op);
+    if (!u || user_output(op) != 0 || u->nout < 2) return fail(-1, "enqueue_gate_multi: op must be a multi-output user gate (cufhe_amd_define_gate_multi)");
+    if (nout != u->nout) return fail(-1, "enqueue_gate_multi: nout must be the definition's output count");
+    if (!outs || !in0) return fail(-1, "null ciphertext");
+    if (g_param_set >= 0 || (g_lvl0_ring == 2048 && outs[0] && outs[0]->level == 0))
+        return fail(-1, "user gates run on the default path only: not with \"param_set\" active or on the N = 2048 ring (\"lvl0_ring\")");
+    const int arity = user_gate_arity(*u);
+    if (arity >= 2 && !in1) return fail(-1, "user gate needs a second operand");
+    if (arity == 3 && !in2) return fail(-1, "user gate needs a third operand");
+    cufhe_amd_ctxt* ins[3] = {in0, arity >= 2 ? in1 : nullptr, arity == 3 ? in2 : nullptr};
+    sched::Scheduler* S = scheduler();
+    int ops[1 << kMaxOutputShift];
+    for (int j = 0; j < nout; j++) {
+        cufhe_amd_ctxt* o = outs[j];
+        if (!o) return fail(-1, "null ciphertext");
+        for (cufhe_amd_ctxt* c : ins)
+            if (o == c) return fail(-1, "enqueue_gate_multi: an output is also an input");
+        for (int i = 0; i < j; i++)
+            if (outs[i] == o) return fail(-1, "enqueue_gate_multi: two outputs are the same ciphertext");
+        if (int rc = sched_check_ctxt(S, o)) return rc;
+        if (o->level > 1) return fail(-1, "gates take lvl0 or lvl1 ciphertexts");
+        if (o->level != outs[0]->level) return fail(-1, "operands of one gate must have the same level");
+        ops[j] = CUFHE_AMD_USER_OP_OUTPUT(op, j);
+    }
+    for (cufhe_amd_ctxt* c : ins) {
+        if (!c) continue;
+        if (int rc = sched_check_ctxt(S, c)) return rc;
+        if (c->level != outs[0]->level) return fail(-1, "operands of one gate must have the same level");
+    }
+    const DeviceState& ds = g_dev[device];
+    if (!ds.keys_ready && !ds.keys2_ready && g_param_set < 0) return fail(-3, "Initialize(ek) has not been called for this device");
+    if (int rc = S->dev(device).record_gate_group(stream, ops, copying != 0, outs, (size_t)nout, ins)) return sched_error(S->dev(device), rc);
     return 0;
 }
 

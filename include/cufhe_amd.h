@@ -142,6 +142,26 @@ int cufhe_amd_define_gate(const int32_t coeffs[3], uint32_t offset, const uint32
  * top half-box [N - N/(2p), N) holds -values[0], so that m = 0 with negative noise still gives values[0].  values: p torus words. */
 int cufhe_amd_test_vector(const uint32_t* values, int p, uint32_t* tv);
 
+/* ---- multi-output user gates: several functions of one linear combination from one blind rotation (many-LUT bootstrapping) ----
+ * A definition of nout = 2^s in {2, 4, 8} outputs has coefficients and offset as above and a REQUIRED test vector TV that interleaves
+ * the nout functions (cufhe_amd_test_vector_multi).  With x as above (nbit = 10) the modulus switch is rounded to multiples of 2^s:
+ *     abar_i = ((a_i + 2^(30 - nbit + s)) >> (31 - nbit + s)) << s,   bbar = 2N - ((b >> (31 - nbit + s)) << s)
+ * (s = 0 gives the rounding of every other gate), the accumulator starts as (0, X^bbar TV), and output j, 0 <= j < nout, is
+ * SampleExtract(j) of the rotated accumulator -- out[m] = a[j - m] (m <= j), -a[N + j - m] (m > j), out[N] = b[j] -- then the key
+ * switch at level 0 (level 0: rotate, extract, key switch; level 1: key switch, rotate, extract).
+ * CUFHE_AMD_USER_OP_OUTPUT(op, j) is the op id of output j of definition op (output 0 is op itself; ids stay below
+ * CUFHE_AMD_USER_OP_BASE + 8 CUFHE_AMD_MAX_USER_GATES).  It is an ordinary single-output op for cufhe_amd_gate, _gate_batch,
+ * _gate_list and _enqueue_gate; outputs of one definition on the same operands in one call (or one dependence level of the scheduler)
+ * share one rotation.  An output j >= nout, or an id of the range with no definition, is refused before any device work.
+ * A definition takes one slot (and one test-vector row) of the CUFHE_AMD_MAX_USER_GATES.  Refused: nout not 2, 4 or 8, a NULL TV,
+ * c0 = 0, a full table, "param_set" active (-1); before cufhe_amd_initialize (-3).  The "param_set" and N = 2048 paths refuse the ops. */
+#define CUFHE_AMD_USER_OP_OUTPUT(op, j) ((op) + (j) * CUFHE_AMD_MAX_USER_GATES)
+int cufhe_amd_define_gate_multi(const int32_t coeffs[3], uint32_t offset, int nout, const uint32_t* test_vector, int* op);
+/* Host helper: the interleaved test vector of nout functions on p messages (as cufhe_amd_test_vector): TV[nout q + j] = values[j][m],
+ * m the box of position nout q under cufhe_amd_test_vector's boxes (the top half-box holds -values[j][0]).  values: [nout][p] torus
+ * words; p a power of two >= 2, nout in {1, 2, 4, 8}, p nout <= N/2.  nout = 1 gives cufhe_amd_test_vector's words. */
+int cufhe_amd_test_vector_multi(const uint32_t* values, int p, int nout, uint32_t* tv);
+
 /* ---- the reference's per-gate API on host-visible ciphertexts ----
  * template<class P> struct Ctxt (include/cufhe_gpu.cuh:102-121): `host_words` is the
  * caller-owned tlwehost storage (n+1 or N+1 words, kept alive by the caller); the handle
@@ -162,6 +182,12 @@ uint32_t* cufhe_amd_ctxt_device_ptr(cufhe_amd_ctxt* c, int device);   /* constan
  * them has retired. */
 int cufhe_amd_enqueue_gate(int device, void* stream, int op, int copying, cufhe_amd_ctxt* out,
                            cufhe_amd_ctxt* in0, cufhe_amd_ctxt* in1, cufhe_amd_ctxt* in2);
+/* The nout outputs of ONE evaluation of a multi-output user gate (cufhe_amd_define_gate_multi): outs[j] receives output j.  The
+ * operands are resolved once, before any output is recorded; the evaluation costs one blind rotation under every schedule.  Refused
+ * (-1, nothing recorded): op not a multi-output definition (output 0 id), nout not its output count, an output that is also an input,
+ * two outputs that are the same handle. */
+int cufhe_amd_enqueue_gate_multi(int device, void* stream, int op, int copying, int nout, cufhe_amd_ctxt* const* outs,
+                                 cufhe_amd_ctxt* in0, cufhe_amd_ctxt* in1, cufhe_amd_ctxt* in2);
 /* TRLWE-level operations through the same scheduler: struct cuFHETRLWElvl1 (include/cufhe_gpu.cuh:124-134) is a
  * ciphertext handle of level 2 ((k+1) N words; cufhe_amd_ctxt_create(2, ...)), and
  * gGateBootstrappingTLWE2TRLWElvl01NTT / gRefresh / gSampleExtractAndKeySwitch (src/cufhe_gates_gpu.cu:86-146;

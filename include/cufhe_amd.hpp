@@ -18,10 +18,12 @@
 // header to take them from <params.hpp>/<cloudkey.hpp> instead (then Initialize(ek) accepts
 // a TFHEpp::EvalKey exactly as the reference does, src/cufhe_gates_gpu.cu:42-47).
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <initializer_list>
 #include <type_traits>
 #include <vector>
 
@@ -349,13 +351,29 @@ CUFHE_AMD_GATE3(NMux, CUFHE_AMD_NMUX)
 /// a defined user gate: x = c0 in0 + c1 in1 + c2 in2 + (0, .., 0, offset) bootstrapped through its test vector
 struct UserGate {
     int op = -1;
+    int nout = 1;       ///< outputs of one evaluation: 1, or 2 / 4 / 8 for a multi-output gate (cufhe_amd_define_gate_multi)
+    /// the op id of output j (a single-output op wherever a built-in op is accepted)
+    int output(int j) const { return CUFHE_AMD_USER_OP_OUTPUT(op, j); }
 };
-/// Define after Initialize; tv: N = 1024 lvl1 torus words (nullptr: the constant mu).  Valid until CleanUp.
-inline UserGate DefineGate(const std::array<int32_t, 3>& coeffs, uint32_t offset, const uint32_t* tv = nullptr)
+/// Define after Initialize; tv: N = 1024 lvl1 torus words (nullptr: the constant mu).  Valid until CleanUp.  nout = 2, 4 or 8: a
+/// multi-output gate whose interleaved tv (TestVectorMulti) is required.
+inline UserGate DefineGate(const std::array<int32_t, 3>& coeffs, uint32_t offset, const uint32_t* tv = nullptr, int nout = 1)
 {
     UserGate g;
-    CUFHE_AMD_CHECK(cufhe_amd_define_gate(coeffs.data(), offset, tv, &g.op));
+    if (nout == 1) CUFHE_AMD_CHECK(cufhe_amd_define_gate(coeffs.data(), offset, tv, &g.op));
+    else CUFHE_AMD_CHECK(cufhe_amd_define_gate_multi(coeffs.data(), offset, nout, tv, &g.op));
+    g.nout = nout;
     return g;
+}
+/// the interleaved test vector of values.size() functions (1, 2, 4 or 8) on p = values[j].size() messages each, p nout <= N/2
+inline std::vector<uint32_t> TestVectorMulti(const std::vector<std::vector<uint32_t>>& values, int p)
+{
+    std::vector<uint32_t> flat;
+    for (const auto& v : values) flat.insert(flat.end(), v.begin(), v.begin() + std::min<size_t>(v.size(), (size_t)p));
+    if (flat.size() != values.size() * (size_t)p) CUFHE_AMD_CHECK(-1);
+    std::vector<uint32_t> tv(1024);
+    CUFHE_AMD_CHECK(cufhe_amd_test_vector_multi(flat.data(), p, (int)values.size(), tv.data()));
+    return tv;
 }
 /// the test vector of a function on values.size() messages (a power of two, 2 .. N/2) with a padding bit, m -> m 2^32 / (2p)
 inline std::vector<uint32_t> TestVector(const std::vector<uint32_t>& values)
@@ -377,6 +395,28 @@ template <class P> inline void Apply(UserGate g, Ctxt<P>& out, Ctxt<P>& in0, Ctx
 { CUFHE_AMD_CHECK(cufhe_amd_enqueue_gate(st.device_id(), st.raw(), g.op, 1, out.handle, in0.handle, in1.handle, in2.handle)); }
 template <class P> inline void gApply(UserGate g, Ctxt<P>& out, Ctxt<P>& in0, Ctxt<P>& in1, Ctxt<P>& in2, Stream st)
 { CUFHE_AMD_CHECK(cufhe_amd_enqueue_gate(st.device_id(), st.raw(), g.op, 0, out.handle, in0.handle, in1.handle, in2.handle)); }
+/// ApplyMulti: all g.nout outputs of one evaluation of a multi-output gate (one rotation), outs[j] <- output j; gApplyMulti: device
+/// buffers only.  No output may be an input, no two outputs the same ciphertext.
+template <class P>
+inline void apply_multi(UserGate g, int copying, std::initializer_list<Ctxt<P>*> outs, Ctxt<P>* in0, Ctxt<P>* in1, Ctxt<P>* in2, Stream st)
+{
+    std::vector<cufhe_amd_ctxt*> h;
+    for (Ctxt<P>* o : outs) h.push_back(o->handle);
+    CUFHE_AMD_CHECK(cufhe_amd_enqueue_gate_multi(st.device_id(), st.raw(), g.op, copying, (int)h.size(), h.data(), in0->handle,
+                                                 in1 ? in1->handle : nullptr, in2 ? in2->handle : nullptr));
+}
+template <class P> inline void ApplyMulti(UserGate g, std::initializer_list<Ctxt<P>*> outs, Ctxt<P>& in0, Stream st)
+{ apply_multi<P>(g, 1, outs, &in0, nullptr, nullptr, st); }
+template <class P> inline void gApplyMulti(UserGate g, std::initializer_list<Ctxt<P>*> outs, Ctxt<P>& in0, Stream st)
+{ apply_multi<P>(g, 0, outs, &in0, nullptr, nullptr, st); }
+template <class P> inline void ApplyMulti(UserGate g, std::initializer_list<Ctxt<P>*> outs, Ctxt<P>& in0, Ctxt<P>& in1, Stream st)
+{ apply_multi<P>(g, 1, outs, &in0, &in1, nullptr, st); }
+template <class P> inline void gApplyMulti(UserGate g, std::initializer_list<Ctxt<P>*> outs, Ctxt<P>& in0, Ctxt<P>& in1, Stream st)
+{ apply_multi<P>(g, 0, outs, &in0, &in1, nullptr, st); }
+template <class P> inline void ApplyMulti(UserGate g, std::initializer_list<Ctxt<P>*> outs, Ctxt<P>& in0, Ctxt<P>& in1, Ctxt<P>& in2, Stream st)
+{ apply_multi<P>(g, 1, outs, &in0, &in1, &in2, st); }
+template <class P> inline void gApplyMulti(UserGate g, std::initializer_list<Ctxt<P>*> outs, Ctxt<P>& in0, Ctxt<P>& in1, Ctxt<P>& in2, Stream st)
+{ apply_multi<P>(g, 0, outs, &in0, &in1, &in2, st); }
 
 // ---- TRLWE-level primitives, include/cufhe_gpu.cuh:123-146,209-216,282-285 ----
 // Same names and operands as the reference.  GateBootstrappingTLWE2TRLWElvl01NTT, Refresh,
