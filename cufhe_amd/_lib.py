@@ -34,6 +34,12 @@ class Lvl2Params(ctypes.Structure):
                [(k, ctypes.c_uint64) for k in ("mu", "bk_words", "ksk_words", "bk_ntt_bytes")]
 
 
+class CbParams(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_uint32) for k in ("n", "N", "k", "l", "Bgbit", "N2", "l2", "Bgbit2", "t", "basebit",
+                                               "lvl0_words", "lvl2_words", "trgsw_words", "trgsw_ntt_doubles")] + \
+               [("privksk_words", ctypes.c_uint64)]
+
+
 class Profile(ctypes.Structure):
     _fields_ = [("blind_rotate_ms", ctypes.c_double), ("blind_rotate_launches", ctypes.c_uint64),
                 ("blind_rotations", ctypes.c_uint64), ("keyswitch_ms", ctypes.c_double),
@@ -149,6 +155,11 @@ SIGNATURES = {
                                                  c_void, c_void, c_void, c_void, ctypes.c_size_t]),
     "cufhe_amd_lvl2_blind_rotate_batch": (ctypes.c_int, [ctypes.c_int, c_void, ctypes.c_size_t, c_void, c_void, ctypes.c_int]),
     "cufhe_amd_lvl2_keyswitch_batch": (ctypes.c_int, [ctypes.c_int, c_void, ctypes.c_size_t, c_void, c_void]),
+    "cufhe_amd_cb_get_params": (ctypes.c_int, [ctypes.POINTER(CbParams)]),
+    "cufhe_amd_cb_initialize": (ctypes.c_int, [c_void, ctypes.c_size_t]),
+    "cufhe_amd_cb_rotate_batch": (ctypes.c_int, [ctypes.c_int, c_void, ctypes.c_size_t, c_void, c_void]),
+    "cufhe_amd_private_keyswitch_batch": (ctypes.c_int, [ctypes.c_int, c_void, ctypes.c_size_t, c_void, c_void]),
+    "cufhe_amd_circuit_bootstrap_batch": (ctypes.c_int, [ctypes.c_int, c_void, ctypes.c_size_t, c_void, c_void, c_void]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -11,7 +11,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import lib, check, Params, Profile, Lvl2Params, SchedStats, PsParams
+from ._lib import lib, check, Params, Profile, Lvl2Params, SchedStats, PsParams, CbParams
 
 # op codes (include/cufhe_amd.h)
 NAND, NOR, XNOR, AND, OR, XOR, ANDNY, ANDYN, ORNY, ORYN, MUX, NMUX, NOT, COPY = range(14)
@@ -192,7 +192,16 @@ class Trlwe(Ctxt):
         _lib.live.add(self)
 
 
-TL_BOOTSTRAP, TL_REFRESH, TL_SEIKS = 100, 101, 102
+class TrgswNtt(Ctxt):
+    """struct cuFHETRGSWNTTlvl1, include/cufhe_gpu.cuh:136-146: a TRGSW in the NTT domain (ciphertext handle of level 3): the selector of
+    CMUXNTT, the output of CircuitBootstrapping."""
+
+    def __init__(self):
+        super().__init__(3)
+        self.trgswhost = self.tlwehost
+
+
+TL_BOOTSTRAP, TL_REFRESH, TL_SEIKS, TL_CMUX, TL_CIRCUIT_BOOTSTRAP = 100, 101, 102, 103, 104
 
 
 def _trlwe_op(op, copying, out, inp, st):
@@ -223,6 +232,24 @@ def gSampleExtractAndKeySwitch(out, inp, st):              # :126-135 (uploads i
 def SampleExtractAndKeySwitch(out, inp, st):               # :137-146
     gSampleExtractAndKeySwitch(out, inp, st)
     CtxtCopyD2H(out, st)
+
+
+def gCMUXNTT(res, cs, c1, c0, st):                         # res = c0 + cs [x] (c1 - c0), device buffers
+    check(lib.cufhe_amd_enqueue_cmux(st.device_id(), st.st(), 0, res._h, cs._h, c1._h, c0._h))
+
+
+def CMUXNTT(res, cs, c1, c0, st):                          # the same from and to the host members
+    check(lib.cufhe_amd_enqueue_cmux(st.device_id(), st.st(), 1, res._h, cs._h, c1._h, c0._h))
+
+
+def gCircuitBootstrapping(out, inp, st):
+    """out (TrgswNtt) <- the circuit bootstrap of lvl0 ciphertext inp, device buffers (cufhe_amd_circuit_bootstrap_batch)"""
+    _trlwe_op(TL_CIRCUIT_BOOTSTRAP, False, out, inp, st)
+
+
+def CircuitBootstrapping(out, inp, st):
+    """the same from inp.tlwehost, the NTT-domain words delivered to out.trgswhost"""
+    _trlwe_op(TL_CIRCUIT_BOOTSTRAP, True, out, inp, st)
 
 
 def CtxtCopyH2D(c, st):
@@ -455,6 +482,35 @@ def lvl2_blind_rotate_batch(tlwe0, acc, count, steps=-1, device=0, stream=None):
 
 def lvl2_keyswitch_batch(tlwe2, tlwe0, count, device=0, stream=None):
     check(lib.cufhe_amd_lvl2_keyswitch_batch(device, stream, count, tlwe2.ptr, tlwe0.ptr))
+
+
+# ---- circuit bootstrapping: lvl0 TLWE -> lvl1 TRGSW (include/cufhe_amd.h) ----
+def cb_params():
+    p = CbParams()
+    check(lib.cufhe_amd_cb_get_params(ctypes.byref(p)))
+    return p
+
+
+def cb_initialize(privksk):
+    """privksk: the private key-switching key lvl2 -> lvl1, uint32 [2][N2 + 1][t][2^basebit - 1][k + 1][N] (2.35 GB)"""
+    privksk = np.ascontiguousarray(privksk, dtype=np.uint32).ravel()
+    check(lib.cufhe_amd_cb_initialize(_ptr(privksk), privksk.size))
+
+
+def cb_rotate_batch(tlwe0, tlwe2, count, device=0, stream=None):
+    """stage 1: tlwe0 [count][n + 1] -> tlwe2 [count][l][N2 + 1] uint64 (two words each in the DeviceBuffer)"""
+    check(lib.cufhe_amd_cb_rotate_batch(device, stream, count, tlwe0.ptr, tlwe2.ptr))
+
+
+def private_keyswitch_batch(tlwe2, trlwe, count, device=0, stream=None):
+    """stage 2: tlwe2 [count][N2 + 1] uint64 -> trlwe [count][2][k + 1][N] uint32"""
+    check(lib.cufhe_amd_private_keyswitch_batch(device, stream, count, tlwe2.ptr, trlwe.ptr))
+
+
+def circuit_bootstrap_batch(tlwe0, count, trgsw=None, trgsw_ntt=None, device=0, stream=None):
+    """tlwe0 [count][n + 1] -> trgsw [count][(k + 1) l][k + 1][N] torus words and / or trgsw_ntt (NTT domain, doubles)"""
+    check(lib.cufhe_amd_circuit_bootstrap_batch(device, stream, count, tlwe0.ptr, trgsw.ptr if trgsw is not None else None,
+                                                trgsw_ntt.ptr if trgsw_ntt is not None else None))
 
 
 def polymul512_batch(a, b, res, count, device=0, stream=None):

@@ -25,6 +25,7 @@
 #include "kernels_lvl2.hip.h"
 #include "kernels_lvl2q.hip.h"
 #include "kernels_ks2.hip.h"
+#include "kernels_pks.hip.h"
 #define CUFHE_AMD_LL_DECLARATIONS_ONLY      // defined in kernels_ll.hip
 #include "kernels_ll.hip.h"
 #include "kernels_ps.hip.h"
@@ -84,6 +85,7 @@ struct DeviceState {
     double* bk2q_ntt = nullptr;        // the same key in the quarter layout
     bool br2q_lds_opt_in = false;
     uint32_t* ksk2 = nullptr;
+    uint32_t* cb_pksk = nullptr;       // circuit bootstrapping: the private key-switching key lvl2 -> lvl1 (cb.inc.h)
     std::vector<EventPair> br_events, ks_events;
     cufhe_amd_profile prof{};
     std::deque<PinnedBlock> staging;
@@ -993,13 +995,16 @@ int lower_gates(const P& p, hipStream_t st, int level, size_t count, GetGate get
 // as ONE launch sequence: sample extracts, one key-switch launch, one blind-rotate launch, scatter; and the CMUXNTT calls of the level
 // (src/bootstrap_gpu.cu:197-285).  Beside what lower_gates uses the path gives se_kernel (the sample extract), trlwe_words, and
 // has_cmux with cmux(): only the small-modulus build of the reference leaves CMUXNTT out (src/cufhe_gates_gpu.cu:68-86).
+int lower_cb_ops(DeviceState& s, hipStream_t st, const GateRef* g, size_t n);   // cb.inc.h
+int cb_ready(const DeviceState& s, bool rotate);
+
 template <class P>
 int lower_trlwe_ops(const P& p, hipStream_t st, const GateRef* g, size_t n)
 {
     DeviceState& s = p.s;
     if (n == 0) return 0;
     constexpr size_t tw = P::trlwe_words;
-    size_t n_se = 0, n_rot = 0, n_t0 = 0, n_cmux = 0;
+    size_t n_se = 0, n_rot = 0, n_t0 = 0, n_cmux = 0, n_cb = 0;
     for (size_t i = 0; i < n; i++) {
         if (!g[i].out || !g[i].in0) return fail(-1, "null operand");
         switch (g[i].op) {
@@ -1011,12 +1016,18 @@ int lower_trlwe_ops(const P& p, hipStream_t st, const GateRef* g, size_t n)
                 if (!g[i].in1 || !g[i].in2) return fail(-1, "CMUXNTT: null operand");
                 n_cmux++;
                 break;
+            case CUFHE_AMD_TL_CIRCUIT_BOOTSTRAP: n_cb++; break;
             default: return fail(-1, "unknown TRLWE-level op");
         }
     }
-    if (n_cmux < n)
+    if (n_cmux + n_cb < n)
         if (int rc = p.ready()) return rc;
     if (n_cmux && !s.ntt_ready) return fail(-3, "Initialize() has not been called for this device");
+    // the circuit bootstraps of this level first, on their own scratch (the stream orders the reuse of the workspace)
+    if (n_cb) {
+        if (int rc = lower_cb_ops(s, st, g, n)) return rc;
+        if (n_cb == n) return 0;
+    }
     Scratch sc;
     const size_t need = (n_se * P::mid_words + n_t0 * P::lvl0_words + n_rot * tw) * 4 + (3 * n + 8) * sizeof(LinDesc) +
                         n_cmux * sizeof(CmuxDesc) + 16384;
@@ -1031,7 +1042,7 @@ int lower_trlwe_ops(const P& p, hipStream_t st, const GateRef* g, size_t n)
             if (int rc = upload_descs(s, sc, cm, &dcm)) return rc;
             if (int rc = p.cmux(st, dcm, cm.size())) return rc;
         }
-        if (n_cmux == n) return 0;
+        if (n_cmux + n_cb == n) return 0;
     }
     uint32_t *t1 = nullptr, *t0 = nullptr, *dump = nullptr;
     if (n_se) if (int rc = sc.alloc((void**)&t1, n_se * P::mid_words * 4)) return rc;
@@ -1040,7 +1051,7 @@ int lower_trlwe_ops(const P& p, hipStream_t st, const GateRef* g, size_t n)
     std::vector<LinDesc> se, ks, rot, scat;
     size_t i_se = 0, i_t0 = 0, i_rot = 0;
     for (size_t i = 0; i < n; i++) {
-        if (g[i].op == CUFHE_AMD_TL_CMUX) continue;
+        if (g[i].op == CUFHE_AMD_TL_CMUX || g[i].op == CUFHE_AMD_TL_CIRCUIT_BOOTSTRAP) continue;
         if (g[i].op == CUFHE_AMD_TL_BOOTSTRAP) {
             rot.push_back({g[i].in0, g[i].in0, nullptr, 1, 0, 0u, 0u});
         } else {
@@ -1171,6 +1182,7 @@ int upload_ksk_padded(DevPtr<uint32_t>& d, const uint32_t* ksk, size_t rows, siz
 
 #include "sched_hip.inc.h"
 #include "lvl2.inc.h"
+#include "cb.inc.h"
 #include "paramsets.inc.h"
 
 extern "C" {
@@ -1325,6 +1337,7 @@ int cufhe_amd_cleanup(void)
         if (s.tvs) { HIP_TRY(hipFree(s.tvs)); s.tvs = nullptr; }
         ps_release(i);
         if (s.keys2_ready) { if (s.bk2_ntt) HIP_TRY(hipFree(s.bk2_ntt)); HIP_TRY(hipFree(s.bk2q_ntt)); HIP_TRY(hipFree(s.ksk2)); }
+        if (s.cb_pksk) { HIP_TRY(hipFree(s.cb_pksk)); s.cb_pksk = nullptr; }
         if (s.tables2) HIP_TRY(hipFree(s.tables2));
         if (s.tables2q) HIP_TRY(hipFree(s.tables2q));
         s.keys2_ready = s.br2_lds_opt_in = s.br2q_lds_opt_in = s.ks2_lds_opt_in = false;

@@ -69,8 +69,9 @@ struct RotDesc2 {          // lvl0 operands, lvl2 result (sample-extracted TLWE)
     uint64_t* out;
     int32_t ca, cb;
     uint32_t off;
-    uint32_t pad;
+    uint32_t pad;          // test vector: 0 = the constant k2Mu, else the constant 2^pad (circuit bootstrapping: desc_mu2)
 };
+__host__ __device__ constexpr uint64_t desc_mu2(uint32_t pad) { return pad ? 1ull << (pad & 63) : k2Mu; }
 struct LinDesc64 {         // out(lvl0) = KS(ca * in0 + cb * in1 + (0, .., off)) on lvl2 TLWEs
     const uint64_t* in0;
     const uint64_t* in1;
@@ -284,13 +285,14 @@ __global__ __launch_bounds__(k2Threads) void blind_rotate_lvl2_kernel(
     uint64_t acc_lo[4], acc_hi[4];
     {
         const uint32_t bbar = *bbar_slot;
+        const uint64_t mu = desc_mu2(d.pad);
 #pragma unroll
         for (int m = 0; m < 4; m++) {
             const uint32_t e0 = (uint32_t)(e_first + 64 * m), e1 = e0 + k2Half;
             const bool n0 = (bbar != 2 * k2N) && ((e0 < (bbar & (k2N - 1))) != ((bbar >> k2Nbit) != 0));
             const bool n1 = (bbar != 2 * k2N) && ((e1 < (bbar & (k2N - 1))) != ((bbar >> k2Nbit) != 0));
-            acc_lo[m] = wj ? (n0 ? 0ull - k2Mu : k2Mu) : 0ull;
-            acc_hi[m] = wj ? (n1 ? 0ull - k2Mu : k2Mu) : 0ull;
+            acc_lo[m] = wj ? (n0 ? 0ull - mu : mu) : 0ull;
+            acc_hi[m] = wj ? (n1 ? 0ull - mu : mu) : 0ull;
         }
     }
     // the LDS copy of acc_j for the rotated reads: sum polynomials (h, o) = (j, 3 j) and (j, 3 j + 1) -- of those the slice

@@ -376,6 +376,7 @@ __global__ __launch_bounds__(kQThreads, 2) void blind_rotate_lvl2q_kernel(
     uint64_t acc[2][2][4];
     {
         const uint32_t bbar = *bbar_slot;     // RotatedTestVector<lvl2param>, include/gatebootstrapping_gpu.cuh:29-52
+        const uint64_t mu = desc_mu2(d.pad);
 #pragma unroll
         for (int s = 0; s < 2; s++)
 #pragma unroll
@@ -383,7 +384,7 @@ __global__ __launch_bounds__(kQThreads, 2) void blind_rotate_lvl2q_kernel(
                 const uint32_t e = (uint32_t)(e_base + 64 * s + kQPoints * t);
                 const bool neg = (bbar != 2 * k2N) && ((e < (bbar & (k2N - 1))) != ((bbar >> k2Nbit) != 0));
                 acc[0][s][t] = 0ull;
-                acc[1][s][t] = neg ? 0ull - k2Mu : k2Mu;
+                acc[1][s][t] = neg ? 0ull - mu : mu;
             }
     }
     char* own = smem + opaque(kQLdsR + 8 * e_base);        // + 16384 j + 512 s + 4096 t: this lane's words in the copy / its exchange slots

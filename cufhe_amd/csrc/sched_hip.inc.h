@@ -549,6 +549,7 @@ int cufhe_amd_enqueue_trlwe_op(int device, void* stream, int op, int copying, cu
         case CUFHE_AMD_TL_BOOTSTRAP: lin = 0; lout = 2; break;
         case CUFHE_AMD_TL_REFRESH: lin = 2; lout = 2; break;
         case CUFHE_AMD_TL_SEIKS: lin = 2; lout = 0; break;
+        case CUFHE_AMD_TL_CIRCUIT_BOOTSTRAP: lin = 0; lout = 3; break;
         default: return fail(-1, "unknown TRLWE-level op");
     }
     sched::Scheduler* S = scheduler();
@@ -556,6 +557,9 @@ int cufhe_amd_enqueue_trlwe_op(int device, void* stream, int op, int copying, cu
     if (int rc = sched_check_ctxt(S, in)) return rc;
     if (in->level != lin || out->level != lout) return fail(-1, "operand levels do not fit the TRLWE-level operation");
     if (!g_dev[device].keys_ready && g_param_set < 0) return fail(-3, "Initialize(ek) has not been called for this device");
+    // circuit bootstrapping (cb.inc.h): refused here, before anything is recorded, when its keys or its parameter set are missing
+    if (op == CUFHE_AMD_TL_CIRCUIT_BOOTSTRAP)
+        if (int rc = cb_ready(g_dev[device], true)) return rc;
     cufhe_amd_ctxt* ins[3] = {in, nullptr, nullptr};
     if (int rc = S->dev(device).record_gate(stream, op, copying != 0, out, ins, 2)) return sched_error(S->dev(device), rc);
     return 0;

@@ -193,7 +193,12 @@ int cufhe_amd_enqueue_gate_multi(int device, void* stream, int op, int copying, 
  * gGateBootstrappingTLWE2TRLWElvl01NTT / gRefresh / gSampleExtractAndKeySwitch (src/cufhe_gates_gpu.cu:86-146;
  * copying != 0: their upload-and-fetch forms) are recorded with their dependences and launched level by level:
  * 4096 Refresh calls on 800 streams (test/test_perf.cc:63-81) become a handful of launches. */
-enum cufhe_amd_trlwe_op { CUFHE_AMD_TL_BOOTSTRAP = 100, CUFHE_AMD_TL_REFRESH = 101, CUFHE_AMD_TL_SEIKS = 102, CUFHE_AMD_TL_CMUX = 103 };
+/* CUFHE_AMD_TL_CIRCUIT_BOOTSTRAP: `in` a lvl0 ciphertext (level 0), `out` a TRGSW holder (level 3) that receives the circuit bootstrap of
+ * `in` in the NTT domain, ready as the selector of cufhe_amd_enqueue_cmux (see cufhe_amd_circuit_bootstrap_batch).  One dependence
+ * level of them is one rotation, one private key-switch and one TRGSW2NTT launch.  Refused before anything is recorded: -3 without
+ * cufhe_amd_cb_initialize or cufhe_amd_lvl2_initialize, -1 with "param_set" active or operands of other levels. */
+enum cufhe_amd_trlwe_op { CUFHE_AMD_TL_BOOTSTRAP = 100, CUFHE_AMD_TL_REFRESH = 101, CUFHE_AMD_TL_SEIKS = 102, CUFHE_AMD_TL_CMUX = 103,
+                          CUFHE_AMD_TL_CIRCUIT_BOOTSTRAP = 104 };
 int cufhe_amd_enqueue_trlwe_op(int device, void* stream, int op, int copying, cufhe_amd_ctxt* out, cufhe_amd_ctxt* in);
 /* CMUXNTT(res, cs, c1, c0, st) (src/cufhe_gates_gpu.cu:68-85; kernel __CMUXNTT__ src/bootstrap_gpu.cu:197-285): res = c0 + cs [x] (c1 - c0),
  * recorded like a gate and ordered against its operands by the scheduler -- as in the reference it returns at once and the
@@ -398,6 +403,38 @@ int cufhe_amd_lvl2_blind_rotate_batch(int device, void* stream, size_t count, co
 int cufhe_amd_lvl2_keyswitch_batch(int device, void* stream, size_t count, const uint64_t* tlwe2,
                                    uint32_t* tlwe0);
 
+/* ---- circuit bootstrapping (CGGI17 section 4, TFHEpp's CircuitBootstrapping): lvl0 TLWE -> lvl1 TRGSW ----
+ * For each input c and r = 0 .. l-1:
+ *   tlwe2_r = SampleExtract(0) of the lvl02 blind rotation of c with the constant test vector mu_r = 2^(63 - (r+1) Bgbit), + mu_r on b
+ *             (message bit * 2^(64 - (r+1) Bgbit));
+ *   row c' l + r of the TRGSW = PrivKS_c'(tlwe2_r), c' = 0, 1, where with abar_i = tlwe2[i] + 2^(64 - t basebit - 1) (i = 0 .. N2,
+ *   i = N2 the b word) and a_ij = (abar_i >> (64 - (j+1) basebit)) & (2^basebit - 1):
+ *             PrivKS_u(tlwe2) = 0 - sum_i sum_j [a_ij != 0] K[u][i][j][a_ij - 1]   (word-wise mod 2^32, both polynomials).
+ * The TRGSW is [(k+1) l][k+1][N] uint32 -- the layout of cufhe_amd_trgsw_to_ntt_batch -- under the default lvl1 key.
+ * K is the caller's private key-switching key, TFHEpp's layout [2][N2 + 1][t][2^basebit - 1][k+1][N] uint32 (2.35 GB):
+ * K[u][i][j][v-1] = TRLWE_s1(v * k2_i * 2^(32 - (j+1) basebit) * f_u), k2_i = s2[i] (i < N2), k2_N2 = -1, f_0 = -s1(X), f_1 = 1.
+ * Every word is deterministic (integer arithmetic only).  Needs cufhe_amd_lvl2_initialize (the lvl02 key) and cufhe_amd_cb_initialize;
+ * default parameter set only ("param_set" active: -1). */
+typedef struct cufhe_amd_cb_params {
+    uint32_t n, N, k, l, Bgbit;        /* output TRGSW: lvl1, l = 3, Bgbit = 6 */
+    uint32_t N2, l2, Bgbit2;           /* the lvl02 rotation */
+    uint32_t t, basebit;               /* private key switching lvl2 -> lvl1: t = 10, basebit = 3 */
+    uint32_t lvl0_words, lvl2_words;   /* n + 1 uint32; N2 + 1 uint64 */
+    uint32_t trgsw_words;              /* (k+1) l (k+1) N uint32 */
+    uint32_t trgsw_ntt_doubles;        /* the same TRGSW in the NTT domain (a level-3 holder's words / 2) */
+    uint64_t privksk_words;            /* 2 (N2 + 1) t (2^basebit - 1) (k+1) N uint32 */
+} cufhe_amd_cb_params;
+int cufhe_amd_cb_get_params(cufhe_amd_cb_params* out);
+/* privksk: host words as above, copied to every device of SetGPUNum (build first, swap last: a failure leaves the keys loaded before) */
+int cufhe_amd_cb_initialize(const uint32_t* privksk, size_t words);
+/* stage 1: tlwe0[count][n+1] -> tlwe2[count][l][N2+1] (uint64, device), mu_r and the b offset applied */
+int cufhe_amd_cb_rotate_batch(int device, void* stream, size_t count, const uint32_t* tlwe0, uint64_t* tlwe2);
+/* stage 2: tlwe2[count][N2+1] -> trlwe[count][2][k+1][N] (uint32, device): PrivKS_0 then PrivKS_1 of each input (no cufhe_amd_lvl2_initialize needed) */
+int cufhe_amd_private_keyswitch_batch(int device, void* stream, size_t count, const uint64_t* tlwe2, uint32_t* trlwe);
+/* both stages: tlwe0[count][n+1] -> trgsw[count][(k+1) l][k+1][N] torus words (may be NULL) and / or trgsw_ntt[count][trgsw_ntt_doubles]
+ * (may be NULL): the words cufhe_amd_trgsw_to_ntt_batch makes of trgsw */
+int cufhe_amd_circuit_bootstrap_batch(int device, void* stream, size_t count, const uint32_t* tlwe0, uint32_t* trgsw, double* trgsw_ntt);
+
 /* ---- other parameter sets (CMakeLists.txt:8-24: USE_80BIT_SECURITY / USE_CGGI19 / USE_CONCRETE select TFHEpp
  * parameter headers at build time; k > 1: src/bootstrap_gpu.cu:402-421; N = 512: include/ntt_gpu/ntt_gpuntt.cuh:283-329)
  * Every set of cufhe_amd/csrc/kernels_ps.hip.h is compiled in and chosen by index: 0 = the default set (the same
@@ -463,7 +500,10 @@ int cufhe_amd_ps_trlwe_op_batch(int set, int device, void* stream, int op, size_
 
 /* ---- measurement ----
  * When enabled, every blind-rotate / key-switch launch is bracketed by HIP events on the
- * stream it runs on; get_profile synchronises and returns accumulated kernel time. */
+ * stream it runs on; get_profile synchronises and returns accumulated kernel time.
+ * Circuit bootstrapping counts in the same fields: its lvl02 rotations as blind rotations (3 per input), its private key-switch
+ * launches as key-switch launches with one key switch per lvl2 TLWE (3 per input).  To split a workload that mixes gates with
+ * circuit bootstraps, profile the two in separate intervals (tools/cb_times.py profiles circuit bootstraps alone). */
 typedef struct cufhe_amd_profile {
     double blind_rotate_ms; uint64_t blind_rotate_launches; uint64_t blind_rotations;
     double keyswitch_ms;    uint64_t keyswitch_launches;    uint64_t keyswitches;

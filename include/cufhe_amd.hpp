@@ -524,6 +524,24 @@ inline void gCMUXNTT(cuFHETRLWElvl1& res, cuFHETRGSWNTTlvl1& cs, cuFHETRLWElvl1&
 {
     CUFHE_AMD_CHECK(cufhe_amd_enqueue_cmux(st.device_id(), st.raw(), 0, res.handle, cs.handle, c1.handle, c0.handle));
 }
+/// Circuit bootstrapping (CGGI17 section 4; include/cufhe_amd.h, cufhe_amd_circuit_bootstrap_batch): a lvl0 ciphertext becomes the
+/// TRGSW selector of CMUXNTT without leaving the device.  Needs the lvl02 key (lvl2::Initialize / cufhe_amd_lvl2_initialize) and the
+/// private key-switching key, [2][N2 + 1][10][7][k + 1][N] uint32 words (2.35 GB), loaded once on every device of SetGPUNum.
+/// Default parameter set only.
+inline void InitializeCircuitBootstrapping(const uint32_t* privksk, size_t words)
+{
+    CUFHE_AMD_CHECK(cufhe_amd_cb_initialize(privksk, words));
+}
+/// CircuitBootstrapping: `in` from in.tlwehost, the NTT-domain TRGSW delivered to out.trgswhost; gCircuitBootstrapping: device buffers
+/// only.  Recorded like CMUXNTT: a CMUXNTT on `out` waits for it, nothing else does.
+inline void CircuitBootstrapping(cuFHETRGSWNTTlvl1& out, Ctxt<TFHEpp::lvl0param>& in, Stream st)
+{
+    CUFHE_AMD_CHECK(cufhe_amd_enqueue_trlwe_op(st.device_id(), st.raw(), CUFHE_AMD_TL_CIRCUIT_BOOTSTRAP, 1, out.handle, in.handle));
+}
+inline void gCircuitBootstrapping(cuFHETRGSWNTTlvl1& out, Ctxt<TFHEpp::lvl0param>& in, Stream st)
+{
+    CUFHE_AMD_CHECK(cufhe_amd_enqueue_trlwe_op(st.device_id(), st.raw(), CUFHE_AMD_TL_CIRCUIT_BOOTSTRAP, 0, out.handle, in.handle));
+}
 #endif  // CUFHE_AMD_SMALL_NTT_MODULUS
 
 #undef CUFHE_AMD_GATE1
