@@ -398,21 +398,26 @@ def gApplyMulti(op, outs, *ins_and_st):
 
 
 # ---- native batched entry points (what bench.py and the parity tests drive) ----
-def gate_batch(ops, level, out, in0, in1=None, in2=None, count=None, device=0, stream=None):
+def gate_batch(ops, level, out, in0, in1=None, in2=None, count=None, device=0, stream=None, stride_words=None, ops_stride=None):
     """ops: one op code or an int array of `count` codes; operands are DeviceBuffers holding
-    `count` contiguous ciphertexts."""
+    `count` contiguous ciphertexts.  stride_words: words from one ciphertext of an operand to the next (default: packed);
+    ops_stride: gate g takes ops[g * ops_stride] (default: 0 for one op code, 1 for an array)."""
     # n + 1 / k N + 1 words of the set the gate entry points run on NOW ("param_set"): the library dispatches level 0 and 1 to that set
     words = lib.cufhe_amd_ctxt_words(level) if level in (0, 1) else 1     # a bad level is rejected by the library
+    if stride_words is None:
+        stride_words = words
     if count is None:
-        count = out.words // words
+        count = out.words // stride_words
     if np.isscalar(ops):
         ops_arr, stride = np.array([ops], dtype=np.int32), 0
     else:
         ops_arr, stride = np.ascontiguousarray(ops, dtype=np.int32), 1
-        assert ops_arr.size >= count
+    if ops_stride is not None:
+        stride = int(ops_stride)
+    assert count == 0 or ops_arr.size > (count - 1) * stride
     check(lib.cufhe_amd_gate_batch(device, stream, level, count, _ptr(ops_arr), stride, out.ptr, in0.ptr,
                                    in1.ptr if in1 is not None else None,
-                                   in2.ptr if in2 is not None else None, words))
+                                   in2.ptr if in2 is not None else None, stride_words))
 
 
 def blind_rotate_batch(tlwe0, acc, count, steps=-1, device=0, stream=None):
