@@ -224,12 +224,27 @@ def gRefresh(out, inp, st):                                # :106-113
     _trlwe_op(TL_REFRESH, False, out, inp, st)
 
 
-def gSampleExtractAndKeySwitch(out, inp, st):              # :126-135 (uploads in.trlwehost, as the reference does)
+TL_SEIKS_AT_BASE, TL_CMUX_ROTATE_BASE = 2048, 4096         # op ids that carry an index / an exponent (include/cufhe_amd.h)
+
+
+def TL_SEIKS_AT(index):
+    """CUFHE_AMD_TL_SEIKS_AT(index): SampleExtract at `index`, then the key switch (packed ROM words)"""
+    return TL_SEIKS_AT_BASE + int(index)
+
+
+def gSampleExtractAndKeySwitch(out, inp, st, index=None):  # :126-135 (uploads in.trlwehost, as the reference does)
+    """index given (0 included): extraction at that coefficient on device buffers only -- the form that follows gCMUXNTT /
+    gCMUXRotateNTT without a copy; the reference's index-less call keeps its upload of inp.trlwehost."""
+    if index is not None:
+        return _trlwe_op(TL_SEIKS_AT(index), False, out, inp, st)
     CtxtCopyH2D(inp, st)
     _trlwe_op(TL_SEIKS, False, out, inp, st)
 
 
-def SampleExtractAndKeySwitch(out, inp, st):               # :137-146
+def SampleExtractAndKeySwitch(out, inp, st, index=0):      # :137-146
+    """index != 0: extraction at that coefficient, from inp.trlwehost to out.tlwehost"""
+    if index != 0:
+        return _trlwe_op(TL_SEIKS_AT(index), True, out, inp, st)
     gSampleExtractAndKeySwitch(out, inp, st)
     CtxtCopyD2H(out, st)
 
@@ -240,6 +255,14 @@ def gCMUXNTT(res, cs, c1, c0, st):                         # res = c0 + cs [x] (
 
 def CMUXNTT(res, cs, c1, c0, st):                          # the same from and to the host members
     check(lib.cufhe_amd_enqueue_cmux(st.device_id(), st.st(), 1, res._h, cs._h, c1._h, c0._h))
+
+
+def gCMUXRotateNTT(res, cs, c, exponent, st):              # res = c + cs [x] (X^exponent c - c), device buffers; res may be c
+    check(lib.cufhe_amd_enqueue_cmux_rotate(st.device_id(), st.st(), 0, res._h, cs._h, c._h, int(exponent)))
+
+
+def CMUXRotateNTT(res, cs, c, exponent, st):               # the same from and to the host members
+    check(lib.cufhe_amd_enqueue_cmux_rotate(st.device_id(), st.st(), 1, res._h, cs._h, c._h, int(exponent)))
 
 
 def gCircuitBootstrapping(out, inp, st):
@@ -447,6 +470,39 @@ def trgsw_to_ntt_batch(trgsw, trgsw_ntt, count, device=0, stream=None):
 
 def cmux_batch(trgsw_ntt, c1, c0, res, count, device=0, stream=None):
     check(lib.cufhe_amd_cmux_batch(device, stream, count, trgsw_ntt.ptr, c1.ptr, c0.ptr, res.ptr))
+
+
+# ---- packed ROM words: exps / src / idx are host integers, one per item ----
+def _i32(values, count):
+    a = np.ascontiguousarray(values, dtype=np.int32).ravel()
+    assert a.size >= count
+    return a
+
+
+def trlwe_rotate_batch(inp, exps, out, count, device=0, stream=None):
+    """out[g] = X^exps[g] inp[g] (negacyclic, 0 <= exps[g] < 2N) on TRLWEs [count][2N]; out must not overlap inp"""
+    e = _i32(exps, count)
+    check(lib.cufhe_amd_trlwe_rotate_batch(device, stream, count, inp.ptr, _ptr(e), out.ptr))
+
+
+def cmux_rotate_batch(trgsw_ntt, exps, c, res, count, device=0, stream=None):
+    """res[g] = c[g] + trgsw [x] (X^exps[g] c[g] - c[g]) with ONE selector for the launch; res may be c"""
+    e = _i32(exps, count)
+    check(lib.cufhe_amd_cmux_rotate_batch(device, stream, count, trgsw_ntt.ptr, _ptr(e), c.ptr, res.ptr))
+
+
+def sample_extract_index_batch(trlwe, idx, tlwe1, count, src=None, device=0, stream=None):
+    """tlwe1[g] = SampleExtract(idx[g])(trlwe[src[g]]) (src None: g), lvl1 TLWEs [count][N+1]"""
+    j = _i32(idx, count)
+    s = _i32(src, count) if src is not None else None
+    check(lib.cufhe_amd_sample_extract_index_batch(device, stream, count, trlwe.ptr, _ptr(s), _ptr(j), tlwe1.ptr))
+
+
+def sample_extract_index_keyswitch_batch(trlwe, idx, tlwe0, count, src=None, device=0, stream=None):
+    """the same followed by the key switch: lvl0 TLWEs [count][n+1]"""
+    j = _i32(idx, count)
+    s = _i32(src, count) if src is not None else None
+    check(lib.cufhe_amd_sample_extract_index_keyswitch_batch(device, stream, count, trlwe.ptr, _ptr(s), _ptr(j), tlwe0.ptr))
 
 
 def polymul_batch(a, b, res, count, device=0, stream=None):

@@ -732,6 +732,15 @@ static_assert(CUFHE_AMD_USER_OP_OUTPUT(CUFHE_AMD_USER_OP_BASE + kMaxUserGates - 
 UserGate g_user[kMaxUserGates];
 std::atomic<int> g_user_count{0};
 bool is_user_op(int op) { return op >= CUFHE_AMD_USER_OP_BASE && op < CUFHE_AMD_USER_OP_BASE + (kMaxUserGates << kMaxOutputShift); }
+// packed ROM words: op ids that carry an index / an exponent (include/cufhe_amd.h)
+static_assert(CUFHE_AMD_TL_SEIKS_AT(0) > CUFHE_AMD_USER_OP_OUTPUT(CUFHE_AMD_USER_OP_BASE + kMaxUserGates - 1, (1 << kMaxOutputShift) - 1) &&
+                  CUFHE_AMD_TL_SEIKS_AT(0) > CUFHE_AMD_TL_CIRCUIT_BOOTSTRAP && CUFHE_AMD_TL_SEIKS_AT(0) >= CUFHE_AMD_NUM_OPS,
+              "SEIKS_AT ids lie above the built-in, TRLWE-level and user ops");
+static_assert(CUFHE_AMD_TL_CMUX_ROTATE(0) > CUFHE_AMD_TL_SEIKS_AT(kN - 1), "CMUX_ROTATE ids lie above the SEIKS_AT ids");
+bool is_seiks_at(int op) { return op >= CUFHE_AMD_TL_SEIKS_AT(0) && op <= CUFHE_AMD_TL_SEIKS_AT(kN - 1); }
+bool is_cmux_rotate(int op) { return op >= CUFHE_AMD_TL_CMUX_ROTATE(0) && op <= CUFHE_AMD_TL_CMUX_ROTATE(2 * kN - 1); }
+int fail_packed_rom_set() { return fail(-1, "packed ROM words (TRLWE rotation, rotating CMUX, indexed SampleExtract) run on the default path only: not with \"param_set\" active"); }
+
 int user_def(int op) { return (op - CUFHE_AMD_USER_OP_BASE) % kMaxUserGates; }      // definition index k of a user op id
 int user_output(int op) { return (op - CUFHE_AMD_USER_OP_BASE) / kMaxUserGates; }   // output j of a user op id
 // the definition of `op`; nullptr when op is not a defined user gate or names an output j >= nout of one
@@ -1004,7 +1013,7 @@ int lower_trlwe_ops(const P& p, hipStream_t st, const GateRef* g, size_t n)
     DeviceState& s = p.s;
     if (n == 0) return 0;
     constexpr size_t tw = P::trlwe_words;
-    size_t n_se = 0, n_rot = 0, n_t0 = 0, n_cmux = 0, n_cb = 0;
+    size_t n_se = 0, n_rot = 0, n_t0 = 0, n_cmux = 0, n_cb = 0, n_cmuxr = 0;
     for (size_t i = 0; i < n; i++) {
         if (!g[i].out || !g[i].in0) return fail(-1, "null operand");
         switch (g[i].op) {
@@ -1017,12 +1026,20 @@ int lower_trlwe_ops(const P& p, hipStream_t st, const GateRef* g, size_t n)
                 n_cmux++;
                 break;
             case CUFHE_AMD_TL_CIRCUIT_BOOTSTRAP: n_cb++; break;
-            default: return fail(-1, "unknown TRLWE-level op");
+            default:
+                // packed ROM words: the indexed extraction joins the level's sample extracts and key switch, the rotating CMUX its CMUXNTT calls
+                if (P::packed_rom && is_seiks_at(g[i].op)) { n_se++; break; }
+                if (P::packed_rom && is_cmux_rotate(g[i].op)) {
+                    if (!g[i].in2) return fail(-1, "rotating CMUX: null operand");
+                    n_cmuxr++;
+                    break;
+                }
+                return fail(-1, "unknown TRLWE-level op");
         }
     }
-    if (n_cmux + n_cb < n)
+    if (n_cmux + n_cmuxr + n_cb < n)
         if (int rc = p.ready()) return rc;
-    if (n_cmux && !s.ntt_ready) return fail(-3, "Initialize() has not been called for this device");
+    if ((n_cmux || n_cmuxr) && !s.ntt_ready) return fail(-3, "Initialize() has not been called for this device");
     // the circuit bootstraps of this level first, on their own scratch (the stream orders the reuse of the workspace)
     if (n_cb) {
         if (int rc = lower_cb_ops(s, st, g, n)) return rc;
@@ -1030,7 +1047,7 @@ int lower_trlwe_ops(const P& p, hipStream_t st, const GateRef* g, size_t n)
     }
     Scratch sc;
     const size_t need = (n_se * P::mid_words + n_t0 * P::lvl0_words + n_rot * tw) * 4 + (3 * n + 8) * sizeof(LinDesc) +
-                        n_cmux * sizeof(CmuxDesc) + 16384;
+                        n_cmux * sizeof(CmuxDesc) + n_cmuxr * sizeof(CmuxRotDesc) + 16384;
     if (int rc = open_scratch(s, st, need, &sc)) return rc;
     if (n_cmux) {      // the CMUXNTT calls of this level: independent of its other operations (the scheduler's contract); needs no key
         if constexpr (P::has_cmux) {
@@ -1044,14 +1061,33 @@ int lower_trlwe_ops(const P& p, hipStream_t st, const GateRef* g, size_t n)
         }
         if (n_cmux + n_cb == n) return 0;
     }
+    if (n_cmuxr) {     // ... and its rotating CMUX calls (cufhe_amd_enqueue_cmux_rotate): in0 = c, in2 = the selector, the exponent in the op id
+        if constexpr (P::packed_rom) {
+            std::vector<CmuxRotDesc> cr;
+            cr.reserve(n_cmuxr);
+            for (size_t i = 0; i < n; i++)
+                if (is_cmux_rotate(g[i].op))
+                    cr.push_back({g[i].in0, g[i].out, (const double*)g[i].in2, (uint32_t)(g[i].op - CUFHE_AMD_TL_CMUX_ROTATE(0)), 0u});
+            CmuxRotDesc* dcr;
+            if (int rc = upload_descs(s, sc, cr, &dcr)) return rc;
+            if (int rc = p.cmux_rotate(st, dcr, cr.size())) return rc;
+        }
+        if (n_cmux + n_cmuxr + n_cb == n) return 0;
+    }
     uint32_t *t1 = nullptr, *t0 = nullptr, *dump = nullptr;
     if (n_se) if (int rc = sc.alloc((void**)&t1, n_se * P::mid_words * 4)) return rc;
     if (n_t0) if (int rc = sc.alloc((void**)&t0, n_t0 * P::lvl0_words * 4)) return rc;
     if (n_rot) if (int rc = sc.alloc((void**)&dump, n_rot * tw * 4)) return rc;
-    std::vector<LinDesc> se, ks, rot, scat;
+    std::vector<LinDesc> se, sei, ks, rot, scat;
     size_t i_se = 0, i_t0 = 0, i_rot = 0;
     for (size_t i = 0; i < n; i++) {
-        if (g[i].op == CUFHE_AMD_TL_CMUX || g[i].op == CUFHE_AMD_TL_CIRCUIT_BOOTSTRAP) continue;
+        if (g[i].op == CUFHE_AMD_TL_CMUX || g[i].op == CUFHE_AMD_TL_CIRCUIT_BOOTSTRAP || is_cmux_rotate(g[i].op)) continue;
+        if (is_seiks_at(g[i].op)) {       // extraction at the id's index (the descriptor's pad), then the level's one key-switch launch
+            uint32_t* a = t1 + i_se++ * P::mid_words;
+            sei.push_back({g[i].in0, g[i].in0, a, 1, 0, 0u, (uint32_t)(g[i].op - CUFHE_AMD_TL_SEIKS_AT(0))});
+            ks.push_back({a, a, g[i].out, 1, 0, 0u, 0u});
+            continue;
+        }
         if (g[i].op == CUFHE_AMD_TL_BOOTSTRAP) {
             rot.push_back({g[i].in0, g[i].in0, nullptr, 1, 0, 0u, 0u});
         } else {
@@ -1068,14 +1104,21 @@ int lower_trlwe_ops(const P& p, hipStream_t st, const GateRef* g, size_t n)
         uint32_t* d = dump + i_rot++ * tw;
         scat.push_back({d, d, g[i].out, 1, 0, 0u, 0u});
     }
-    LinDesc *dse, *dks, *drot, *dscat;
+    LinDesc *dse, *dsei, *dks, *drot, *dscat;
     if (int rc = upload_descs(s, sc, se, &dse)) return rc;
+    if (int rc = upload_descs(s, sc, sei, &dsei)) return rc;
     if (int rc = upload_descs(s, sc, ks, &dks)) return rc;
     if (int rc = upload_descs(s, sc, rot, &drot)) return rc;
     if (int rc = upload_descs(s, sc, scat, &dscat)) return rc;
     if (!se.empty()) {
         hipLaunchKernelGGL(P::se_kernel, dim3((unsigned)(se.size() < 2048 ? se.size() : 2048)), dim3(256), 0, st, dse, (int)se.size());
         HIP_TRY(hipGetLastError());
+    }
+    if constexpr (P::packed_rom) {
+        if (!sei.empty()) {
+            hipLaunchKernelGGL(sample_extract_index_desc_kernel, dim3((unsigned)(sei.size() < 2048 ? sei.size() : 2048)), dim3(256), 0, st, dsei, (int)sei.size());
+            HIP_TRY(hipGetLastError());
+        }
     }
     if (int rc = p.keyswitch(st, dks, ks.size())) return rc;
     if (int rc = p.rotate(st, drot, rot.size(), P::n, dump)) return rc;
@@ -1089,7 +1132,7 @@ struct BasePath {
     using Mid = uint32_t;
     static constexpr int lvl0_words = kLvl0Words, mid_words = kLvl1Words, n = kLvl0N;
     static constexpr uint32_t ks_mu = kMu;
-    static constexpr bool lvl1_gates = true, has_cmux = true, user_gates = true;
+    static constexpr bool lvl1_gates = true, has_cmux = true, user_gates = true, packed_rom = true;
     static constexpr size_t trlwe_words = 2 * kN;
     static constexpr auto se_kernel = sample_extract_desc_kernel;
     DeviceState& s;
@@ -1100,6 +1143,13 @@ struct BasePath {
     {
         const unsigned blocks = (unsigned)((count + kNttWavesPerBlock - 1) / kNttWavesPerBlock);
         hipLaunchKernelGGL(cmux_desc_kernel, dim3(blocks), dim3(kNttThreads), kNttLdsBytes, st, d, (int)count, s.tables);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    }
+    int cmux_rotate(hipStream_t st, const CmuxRotDesc* d, size_t count) const
+    {
+        const unsigned blocks = (unsigned)((count + kNttWavesPerBlock - 1) / kNttWavesPerBlock);
+        hipLaunchKernelGGL(cmux_rotate_desc_kernel, dim3(blocks), dim3(kNttThreads), kNttLdsBytes, st, d, (int)count, s.tables);
         HIP_TRY(hipGetLastError());
         return 0;
     }
@@ -1704,6 +1754,124 @@ int cufhe_amd_sample_extract_keyswitch_batch(int device, void* stream, size_t co
     if (int rc = sc.alloc((void**)&t1, count * kLvl1Words * sizeof(uint32_t))) return rc;
     hipLaunchKernelGGL(sample_extract_kernel, dim3((unsigned)(count < 2048 ? count : 2048)), dim3(256), 0, st, t1, trlwe, (int)count);
     HIP_TRY(hipGetLastError());
+    std::vector<LinDesc> ks(count);
+    for (size_t g = 0; g < count; g++)
+        ks[g] = {t1 + g * kLvl1Words, t1 + g * kLvl1Words, tlwe0 + g * kLvl0Words, 1, 0, 0u, 0u};
+    LinDesc* d;
+    if (int rc = upload_descs(s, sc, ks, &d)) return rc;
+    return launch_keyswitch(s, st, d, count);
+}
+
+// ---- packed ROM words ----
+int cufhe_amd_trlwe_rotate_batch(int device, void* stream, size_t count, const uint32_t* in, const int32_t* exps, uint32_t* out)
+{
+    if (g_param_set >= 0) return fail_packed_rom_set();
+    if (int rc = check_device(device)) return rc;
+    if (!in || !exps || !out) return fail(-1, "null pointer");
+    // the kernel gathers from `in` while other waves store to `out`: any overlap of the two arrays is refused
+    if (count && in < out + count * 2 * kN && out < in + count * 2 * kN) return fail(-1, "trlwe_rotate_batch: out must not overlap in");
+    for (size_t g = 0; g < count; g++)
+        if (exps[g] < 0 || exps[g] >= 2 * kN) return fail(-1, "trlwe_rotate_batch: exponent outside [0, 2N)");
+    if (count == 0) return 0;
+    if (int rc = use_device(device)) return rc;
+    DeviceState& s = g_dev[device];
+    hipStream_t st = (hipStream_t)stream;
+    Scratch sc;
+    if (int rc = open_scratch(s, st, count * sizeof(int32_t) + 4096, &sc)) return rc;
+    int32_t* dexps;
+    if (int rc = upload_descs(s, sc, std::vector<int32_t>(exps, exps + count), &dexps)) return rc;
+    const unsigned blocks = (unsigned)((count + kRotWavesPerBlock - 1) / kRotWavesPerBlock);
+    hipLaunchKernelGGL(trlwe_rotate_kernel, dim3(blocks), dim3(64 * kRotWavesPerBlock), 0, st, out, in, dexps, (int)count);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int cufhe_amd_cmux_rotate_batch(int device, void* stream, size_t count, const double* trgsw_ntt, const int32_t* exps,
+                                const uint32_t* c, uint32_t* res)
+{
+    if (g_param_set >= 0) return fail_packed_rom_set();
+    if (int rc = check_device(device)) return rc;
+    if (!trgsw_ntt || !exps || !c || !res) return fail(-1, "null pointer");
+    // a wave reads its whole item before it stores: res == c is the in-place form; a partial overlap would cross items
+    if (count && res != c && c < res + count * 2 * kN && res < c + count * 2 * kN)
+        return fail(-1, "cmux_rotate_batch: res must be c itself or not overlap it");
+    for (size_t g = 0; g < count; g++)
+        if (exps[g] < 0 || exps[g] >= 2 * kN) return fail(-1, "cmux_rotate_batch: exponent outside [0, 2N)");
+    if (count == 0) return 0;
+    if (int rc = use_device(device)) return rc;
+    {
+        std::lock_guard<std::mutex> lk(g_mu);
+        if (int rc = ensure_ntt(device)) return rc;
+    }
+    DeviceState& s = g_dev[device];
+    hipStream_t st = (hipStream_t)stream;
+    Scratch sc;
+    if (int rc = open_scratch(s, st, count * sizeof(int32_t) + 4096, &sc)) return rc;
+    int32_t* dexps;
+    if (int rc = upload_descs(s, sc, std::vector<int32_t>(exps, exps + count), &dexps)) return rc;
+    const unsigned blocks = (unsigned)((count + kNttWavesPerBlock - 1) / kNttWavesPerBlock);
+    hipLaunchKernelGGL(cmux_rotate_kernel, dim3(blocks), dim3(kNttThreads), kNttLdsBytes, st, res, trgsw_ntt, c, dexps, (int)count, s.tables);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// the indexed extraction of both entries below into tlwe1 (device, [count][N+1]); sc: the open scratch of the call
+static int launch_sample_extract_index(DeviceState& s, Scratch& sc, size_t count, const uint32_t* trlwe, const int32_t* src,
+                                       const int32_t* idx, uint32_t* tlwe1)
+{
+    std::vector<int32_t> h(2 * count);      // [src | idx], one staged copy
+    for (size_t g = 0; g < count; g++) {
+        h[g] = src ? src[g] : (int32_t)g;
+        h[count + g] = idx[g];
+    }
+    int32_t* d;
+    if (int rc = upload_descs(s, sc, h, &d)) return rc;
+    hipLaunchKernelGGL(sample_extract_index_kernel, dim3((unsigned)(count < 2048 ? count : 2048)), dim3(256), 0, sc.st, tlwe1, trlwe, d,
+                       d + count, (int)count);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+static int check_extract_index_args(size_t count, const uint32_t* trlwe, const int32_t* src, const int32_t* idx, const uint32_t* out)
+{
+    if (!trlwe || !idx || !out) return fail(-1, "null pointer");
+    if (count > (size_t)INT32_MAX) return fail(-1, "sample_extract_index: count exceeds the index type of src");
+    for (size_t g = 0; g < count; g++) {
+        if (idx[g] < 0 || idx[g] >= kN) return fail(-1, "sample_extract_index: index outside [0, N)");
+        if (src && src[g] < 0) return fail(-1, "sample_extract_index: negative source index");
+    }
+    return 0;
+}
+
+int cufhe_amd_sample_extract_index_batch(int device, void* stream, size_t count, const uint32_t* trlwe, const int32_t* src,
+                                         const int32_t* idx, uint32_t* tlwe1)
+{
+    if (g_param_set >= 0) return fail_packed_rom_set();
+    if (int rc = check_device(device)) return rc;
+    if (int rc = check_extract_index_args(count, trlwe, src, idx, tlwe1)) return rc;
+    if (count == 0) return 0;
+    if (int rc = use_device(device)) return rc;
+    DeviceState& s = g_dev[device];
+    Scratch sc;
+    if (int rc = open_scratch(s, (hipStream_t)stream, 2 * count * sizeof(int32_t) + 4096, &sc)) return rc;
+    return launch_sample_extract_index(s, sc, count, trlwe, src, idx, tlwe1);
+}
+
+int cufhe_amd_sample_extract_index_keyswitch_batch(int device, void* stream, size_t count, const uint32_t* trlwe, const int32_t* src,
+                                                   const int32_t* idx, uint32_t* tlwe0)
+{
+    if (g_param_set >= 0) return fail_packed_rom_set();
+    if (int rc = check_device(device)) return rc;
+    DeviceState& s = g_dev[device];
+    if (!s.keys_ready) return fail(-3, "Initialize(ek) has not been called for this device");
+    if (int rc = check_extract_index_args(count, trlwe, src, idx, tlwe0)) return rc;
+    if (count == 0) return 0;
+    if (int rc = use_device(device)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    Scratch sc;
+    if (int rc = open_scratch(s, st, count * (kLvl1Words * sizeof(uint32_t) + sizeof(LinDesc) + 2 * sizeof(int32_t)) + 8192, &sc)) return rc;
+    uint32_t* t1;
+    if (int rc = sc.alloc((void**)&t1, count * kLvl1Words * sizeof(uint32_t))) return rc;
+    if (int rc = launch_sample_extract_index(s, sc, count, trlwe, src, idx, t1)) return rc;
     std::vector<LinDesc> ks(count);
     for (size_t g = 0; g < count; g++)
         ks[g] = {t1 + g * kLvl1Words, t1 + g * kLvl1Words, tlwe0 + g * kLvl0Words, 1, 0, 0u, 0u};

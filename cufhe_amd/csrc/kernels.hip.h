@@ -13,6 +13,9 @@
 //                                                   (small launches: lowest latency)
 //   sample_extract_kernel, cmux_kernel             SEIandKS / Refresh / CMUXNTT pieces
 //                                                   src/keyswitch_gpu.cu:26-40, src/bootstrap_gpu.cu:197-285
+//   sample_extract_index_kernel, trlwe_rotate_kernel, cmux_rotate_kernel
+//                                                  packed ROM words: __SampleExtractIndex__ at a run-time index
+//                                                  (src/bootstrap_gpu.cu:366-381), X^e on a TRLWE, the CMUX of c and X^e c
 //   polymul_kernel         the NTT product check of test/test_polynomial_mult_1024.cu:76-99
 //
 // Execution model (not the reference's one-block-per-gate/one-launch-per-gate): a launch
@@ -905,23 +908,97 @@ __global__ __launch_bounds__(256) void sample_extract_desc_kernel(const LinDesc*
 }
 
 // ----------------------------------------------------------------------------------
+// Packed ROM words: extraction at a caller's index and rotation by X^e, 0 <= e < 2N.
+// ----------------------------------------------------------------------------------
+// __SampleExtractIndex__<P,index> (src/bootstrap_gpu.cu:366-381) with the index a run-time value, 0 <= j < N, on a TRLWE in global
+// memory: out[m] = a[j - m] (m <= j), -a[N + j - m] (m > j), out[N] = b[j] -- the formula of extract_more (kernels_common.hip.h).
+__device__ __forceinline__ void sample_extract_index_block(uint32_t* __restrict__ o, const uint32_t* __restrict__ in, int j)
+{
+    for (int m = threadIdx.x; m <= kN; m += blockDim.x)
+        o[m] = (m == kN) ? in[kN + j] : (m <= j ? in[j - m] : 0u - in[kN + j - m]);
+}
+// tlwe1[g] = SampleExtract(idx[g])(trlwe[src[g]]): several outputs may name one source; src[g] is the caller's contract (no length here)
+__global__ __launch_bounds__(256) void sample_extract_index_kernel(uint32_t* __restrict__ tlwe1, const uint32_t* __restrict__ trlwe,
+                                                                   const int32_t* __restrict__ src, const int32_t* __restrict__ idx, int count)
+{
+    for (int g = blockIdx.x; g < count; g += gridDim.x)
+        sample_extract_index_block(tlwe1 + (size_t)g * kLvl1Words, trlwe + (size_t)src[g] * 2 * kN, idx[g] & (kN - 1));
+}
+// the same with one descriptor per output: in0 = trlwe (2N words), out = lvl1 TLWE (N + 1 words), pad = the index
+__global__ __launch_bounds__(256) void sample_extract_index_desc_kernel(const LinDesc* __restrict__ descs, int count)
+{
+    for (int g = blockIdx.x; g < count; g += gridDim.x)
+        sample_extract_index_block(descs[g].out, descs[g].in0, (int)(descs[g].pad & (kN - 1)));
+}
+
+// Coefficient idx of X^e p in Z[X]/(X^N + 1), e = elo + N ehi: p[idx - elo] for idx >= elo, the negacyclic wrap -p[idx - elo + N]
+// below, and X^N = -1 flips both.  Across a wave (idx = lane + 64 r) the addresses are contiguous except at the wrap.
+__device__ __forceinline__ uint32_t rotated_coef(const uint32_t* p, int idx, int elo, bool ehi)
+{
+    const uint32_t v = p[(idx - elo) & (kN - 1)];
+    return ((idx < elo) != ehi) ? 0u - v : v;
+}
+// out[g] = X^(exps[g]) in[g] on both polynomials of TRLWEs [count][2N], one wave per TRLWE; out must not overlap in (the host refuses it)
+constexpr int kRotWavesPerBlock = 4;
+__global__ __launch_bounds__(64 * kRotWavesPerBlock) void trlwe_rotate_kernel(uint32_t* __restrict__ out, const uint32_t* __restrict__ in,
+                                                                              const int32_t* __restrict__ exps, int count)
+{
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int g = blockIdx.x * kRotWavesPerBlock + wave;
+    if (g >= count) return;
+    const uint32_t e = __builtin_amdgcn_readfirstlane((uint32_t)exps[g]);
+    const int elo = (int)(e & (kN - 1));
+    const bool ehi = ((e >> kNbit) & 1u) != 0;
+    const uint32_t* p = in + (size_t)g * 2 * kN;
+    uint32_t* o = out + (size_t)g * 2 * kN;
+#pragma unroll
+    for (int j = 0; j < 2; j++) {
+        uint32_t v[kRegs];
+#pragma unroll
+        for (int r = 0; r < kRegs; r++) v[r] = rotated_coef(p + j * kN, lane + 64 * r, elo, ehi);
+#pragma unroll
+        for (int r = 0; r < kRegs; r++) o[j * kN + lane + 64 * r] = v[r];
+    }
+}
+
+// ----------------------------------------------------------------------------------
 // CMUX against a caller-supplied TRGSW in the NTT domain (one wave per CMUX):
 // res = c0 + trgsw [x] (c1 - c0), __CMUXNTT__ src/bootstrap_gpu.cu:197-285.  trgsw_ntt holds
 // (k+1)l rows of two polynomials in the layout bk_to_ntt_kernel writes.
 // ----------------------------------------------------------------------------------
+// ROT: the rotating CMUX res = c + trgsw [x] (X^e c - c), 0 <= e < 2N wave-uniform -- one blind-rotation step against the caller's
+// key.  There is no c1 in memory (p1 is not read): the rotated operand is gathered from p0 while the difference is decomposed, so the
+// words are those of cmux_wave<false> with c1 = X^e c.  In place (o == p0, the d address bits of a packed ROM are d steps on one
+// buffer) is safe because the wave owns its whole item and every read of p0 -- the gathers and the subtrahends here, for both
+// polynomials, and `base` below -- is issued before the first store to o: the stores take the inverse transforms of sums that are
+// complete only after the last gather has been consumed, and o / p0 are not __restrict__, so the compiler keeps that order too.
+template <bool ROT = false>
 __device__ __forceinline__ void cmux_wave(uint32_t* o, const double2* key, const uint32_t* p1, const uint32_t* p0,
-                                          const WaveCtx& ctx, int lane)
+                                          const WaveCtx& ctx, int lane, uint32_t rot_e = 0)
 {
     double A0[kRegs], A1[kRegs];
 #pragma unroll
     for (int r = 0; r < kRegs; r++) { A0[r] = 0.0; A1[r] = 0.0; }
+    const int elo = (int)(rot_e & (kN - 1));
+    const bool ehi = ((rot_e >> kNbit) & 1u) != 0;
 #pragma unroll 1
     for (int j = 0; j < 2; j++) {
         uint32_t temp[kRegs];
+        if constexpr (ROT) {
+            uint32_t rot[kRegs], own[kRegs];
 #pragma unroll
-        for (int r = 0; r < kRegs; r++) {
-            const int e = j * kN + lane + 64 * r;
-            temp[r] = (p1[e] - p0[e] + decomp_offset()) ^ decomp_signmask();   // TRLWESubAndDecomposition :162-195
+            for (int r = 0; r < kRegs; r++) {      // all 32 reads in flight together; lane + 64 r - elo mod N: contiguous per row except at the wrap
+                rot[r] = rotated_coef(p0 + j * kN, lane + 64 * r, elo, ehi);
+                own[r] = p0[j * kN + lane + 64 * r];
+            }
+#pragma unroll
+            for (int r = 0; r < kRegs; r++) temp[r] = (rot[r] - own[r] + decomp_offset()) ^ decomp_signmask();
+        } else {
+#pragma unroll
+            for (int r = 0; r < kRegs; r++) {
+                const int e = j * kN + lane + 64 * r;
+                temp[r] = (p1[e] - p0[e] + decomp_offset()) ^ decomp_signmask();   // TRLWESubAndDecomposition :162-195
+            }
         }
 #pragma unroll 1
         for (int d = 0; d < kL; d++) {
@@ -989,6 +1066,44 @@ __global__ __launch_bounds__(kNttThreads) void cmux_desc_kernel(const CmuxDesc* 
     const WaveCtx ctx = make_wave_ctx(smem, kLdsTableBytes + wave * kTileBytes, 0, gt, lane);
     const CmuxDesc d = descs[g];
     cmux_wave(d.res, (const double2*)d.trgsw_ntt, d.c1, d.c0, ctx, lane);
+}
+
+// The rotating CMUX of a batch: res[g] = c[g] + trgsw [x] (X^(exps[g]) c[g] - c[g]) with ONE selector for the launch (an address bit
+// of a packed ROM acts on every TRLWE of the table); res may be c
+__global__ __launch_bounds__(kNttThreads) void cmux_rotate_kernel(
+    uint32_t* res, const double* __restrict__ trgsw_ntt, const uint32_t* c, const int32_t* __restrict__ exps, int count,
+    const NttTables* __restrict__ gt)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    load_tables_to_lds((double*)smem, gt);
+    __syncthreads();
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int g = blockIdx.x * kNttWavesPerBlock + wave;
+    if (g >= count) return;
+    const WaveCtx ctx = make_wave_ctx(smem, kLdsTableBytes + wave * kTileBytes, 0, gt, lane);
+    const uint32_t e = __builtin_amdgcn_readfirstlane((uint32_t)exps[g]);
+    cmux_wave<true>(res + (size_t)g * 2 * kN, (const double2*)trgsw_ntt, nullptr, c + (size_t)g * 2 * kN, ctx, lane, e);
+}
+
+// ... and on per-operation pointers, beside cmux_desc_kernel: the scheduler's cufhe_amd_enqueue_cmux_rotate calls of one dependence level
+struct CmuxRotDesc {
+    const uint32_t* c;
+    uint32_t* res;
+    const double* trgsw_ntt;
+    uint32_t e;
+    uint32_t pad;
+};
+__global__ __launch_bounds__(kNttThreads) void cmux_rotate_desc_kernel(const CmuxRotDesc* __restrict__ descs, int count, const NttTables* __restrict__ gt)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    load_tables_to_lds((double*)smem, gt);
+    __syncthreads();
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int g = blockIdx.x * kNttWavesPerBlock + wave;
+    if (g >= count) return;
+    const WaveCtx ctx = make_wave_ctx(smem, kLdsTableBytes + wave * kTileBytes, 0, gt, lane);
+    const CmuxRotDesc d = descs[g];
+    cmux_wave<true>(d.res, (const double2*)d.trgsw_ntt, nullptr, d.c, ctx, lane, __builtin_amdgcn_readfirstlane(d.e));
 }
 
 // out = ca*in0 + cb*in1 + (0,..,off) over `words` words; grid-stride over ciphertexts

@@ -545,7 +545,10 @@ int cufhe_amd_enqueue_trlwe_op(int device, void* stream, int op, int copying, cu
     if (int rc = check_device(device)) return rc;
     if (!out || !in) return fail(-1, "null ciphertext");
     int lin, lout;
-    switch (op) {
+    if (is_seiks_at(op)) {                 // CUFHE_AMD_TL_SEIKS_AT(j): an id outside [0, N) lies outside the range and is unknown below
+        if (g_param_set >= 0) return fail_packed_rom_set();
+        lin = 2; lout = 0;
+    } else switch (op) {
         case CUFHE_AMD_TL_BOOTSTRAP: lin = 0; lout = 2; break;
         case CUFHE_AMD_TL_REFRESH: lin = 2; lout = 2; break;
         case CUFHE_AMD_TL_SEIKS: lin = 2; lout = 0; break;
@@ -609,6 +612,35 @@ int cufhe_amd_enqueue_cmux(int device, void* stream, int copying, cufhe_amd_ctxt
     if (res->level != 2 || c1->level != 2 || c0->level != 2 || cs->level != 3) return fail(-1, "CMUXNTT takes TRLWEs and a TRGSW in the NTT domain");
     cufhe_amd_ctxt* ins[3] = {c1, c0, cs};
     if (int rc = S->dev(device).record_gate(stream, CUFHE_AMD_TL_CMUX, copying != 0, res, ins, 2)) return sched_error(S->dev(device), rc);
+    return 0;
+}
+
+/* The rotating CMUX res = c + cs [x] (X^exponent c - c), recorded like CMUXNTT with the exponent in the op id (CUFHE_AMD_TL_CMUX_ROTATE):
+ * operands (c, -, cs).  res may be c: TRLWE outputs are never renamed, so the d steps of d address bits run in place on one buffer,
+ * each a dependence level behind the one before. */
+int cufhe_amd_enqueue_cmux_rotate(int device, void* stream, int copying, cufhe_amd_ctxt* res, cufhe_amd_ctxt* cs, cufhe_amd_ctxt* c,
+                                  int exponent)
+{
+    if (g_param_set >= 0) return fail_packed_rom_set();
+    if (int rc = check_device(device)) return rc;
+    if (!res || !cs || !c) return fail(-1, "null operand");
+    if (exponent < 0 || exponent >= 2 * kN) return fail(-1, "rotating CMUX: exponent outside [0, 2N)");
+    {
+        std::lock_guard<std::mutex> lk(g_sched_mu);
+        sched::Scheduler* S = scheduler();
+        for (cufhe_amd_ctxt* x : {res, cs, c})
+            if (int rc = sched_check_ctxt(S, x)) return rc;
+        if (res->level != 2 || c->level != 2 || cs->level != 3) return fail(-1, "the rotating CMUX takes TRLWEs and a TRGSW in the NTT domain");
+    }
+    {
+        std::lock_guard<std::mutex> lk(g_mu);
+        HIP_TRY(hipSetDevice(phys_device(device)));
+        if (int rc = ensure_ntt(device)) return rc;
+    }
+    std::lock_guard<std::mutex> lk(g_sched_mu);
+    sched::Scheduler* S = scheduler();
+    cufhe_amd_ctxt* ins[3] = {c, nullptr, cs};
+    if (int rc = S->dev(device).record_gate(stream, CUFHE_AMD_TL_CMUX_ROTATE(exponent), copying != 0, res, ins, 2)) return sched_error(S->dev(device), rc);
     return 0;
 }
 

@@ -208,6 +208,26 @@ int cufhe_amd_enqueue_trlwe_op(int device, void* stream, int op, int copying, cu
  * the host (the reference's only form); 0: device buffers only.  Needs Initialize() only, like the reference. */
 int cufhe_amd_enqueue_cmux(int device, void* stream, int copying, cufhe_amd_ctxt* res, cufhe_amd_ctxt* cs,
                            cufhe_amd_ctxt* c1, cufhe_amd_ctxt* c0);
+/* ---- packed ROM words, recorded forms (no counterpart in the reference; default parameter set only) ----
+ * Op ids that carry a number, the way CUFHE_AMD_USER_OP_OUTPUT does.  Ranges (none overlaps enum cufhe_amd_op, enum cufhe_amd_trlwe_op
+ * or the user-gate range CUFHE_AMD_USER_OP_BASE .. CUFHE_AMD_USER_OP_BASE + 8 CUFHE_AMD_MAX_USER_GATES = 1000 .. 1512; capi.hip asserts it):
+ *     CUFHE_AMD_TL_SEIKS_AT(j),   0 <= j < N:   2048 .. 3071
+ *     CUFHE_AMD_TL_CMUX_ROTATE(e), 0 <= e < 2N: 4096 .. 6143   (what cufhe_amd_enqueue_cmux_rotate records; not an op of _enqueue_trlwe_op)
+ * CUFHE_AMD_TL_SEIKS_AT(j): an op of cufhe_amd_enqueue_trlwe_op with `in` of level 2 and `out` of level 0: __SampleExtractIndex__ at
+ * index j (src/bootstrap_gpu.cu:366-381: out[m] = a[j - m] for m <= j, -a[N + j - m] for m > j, out[N] = b[j]) then the key switch.
+ * CUFHE_AMD_TL_SEIKS_AT(0) gives exactly the words of CUFHE_AMD_TL_SEIKS.  An id whose index is outside [0, N) lies outside the range
+ * and is refused like any unknown op (-1, nothing recorded); "param_set" active: -1. */
+#define CUFHE_AMD_TL_SEIKS_AT_BASE 2048
+#define CUFHE_AMD_TL_SEIKS_AT(j) (CUFHE_AMD_TL_SEIKS_AT_BASE + (j))
+#define CUFHE_AMD_TL_CMUX_ROTATE_BASE 4096
+#define CUFHE_AMD_TL_CMUX_ROTATE(e) (CUFHE_AMD_TL_CMUX_ROTATE_BASE + (e))
+/* The rotating CMUX res = c + cs [x] (X^exponent c - c), 0 <= exponent < 2N: the words of CMUXNTT(res, cs, X^exponent c, c) -- one
+ * blind-rotation step against the caller's selector -- without X^exponent c ever being stored.  Recorded like cufhe_amd_enqueue_cmux:
+ * res, c TRLWE handles (level 2), cs a TRGSW holder (level 3); res may be c (the d low address bits of a packed ROM are d steps on the
+ * same buffer).  Needs Initialize() only.  Refused with -1 and nothing recorded: an exponent outside [0, 2N), other levels,
+ * "param_set" active. */
+int cufhe_amd_enqueue_cmux_rotate(int device, void* stream, int copying, cufhe_amd_ctxt* res, cufhe_amd_ctxt* cs,
+                                  cufhe_amd_ctxt* c, int exponent);
 /* CtxtCopyH2D / CtxtCopyD2H (include/cufhe_gpu.cuh:193-207), ordered with the recorded gates */
 int cufhe_amd_enqueue_copy(int device, void* stream, cufhe_amd_ctxt* c, int to_device);
 int cufhe_amd_flush(int device);                        /* launch what is recorded, do not wait */
@@ -285,6 +305,30 @@ int cufhe_amd_trgsw_to_ntt(int device, void* stream, const uint32_t* trgsw_host,
 /* CMUXNTT (src/bootstrap_gpu.cu:197-285): res = c0 + trgsw [x] (c1 - c0), TRLWEs [count][2N]; res may be c0 or c1 */
 int cufhe_amd_cmux_batch(int device, void* stream, size_t count, const double* trgsw_ntt,
                          const uint32_t* c1, const uint32_t* c0, uint32_t* res);
+/* ---- packed ROM words (no counterpart in the reference beyond the index form of __SampleExtractIndex__) ----
+ * One TRLWE holds N / w words of w bits; the low address bits rotate the wanted word to the front, the high ones pick the TRLWE with
+ * CMUXNTT, and the w bits come out as lvl0 ciphertexts.  X^e p is the negacyclic product in Z_2^32[X]/(X^N + 1), 0 <= e < 2N:
+ * coefficient i of X^e p is p[i - e'] for i >= e' and -p[i - e' + N] for i < e' (e' = e mod N), all negated when e >= N.
+ * Default parameter set only: with "param_set" active every entry below returns -1 before any device work.  exps / src / idx are HOST
+ * arrays, staged through the stream's workspace (no allocation per call); a value out of range returns -1 before any device work.
+ * out[g] = X^(exps[g]) in[g] on both polynomials of TRLWEs [count][2N].  out must not overlap in (-1).  Needs no key. */
+int cufhe_amd_trlwe_rotate_batch(int device, void* stream, size_t count, const uint32_t* in, const int32_t* exps, uint32_t* out);
+/* The rotating CMUX: res[g] = c[g] + trgsw [x] (X^(exps[g]) c[g] - c[g]), TRLWEs [count][2N]: the words of cufhe_amd_cmux_batch with
+ * c1 = X^e c and c0 = c, the rotated operand never written to memory.  ONE selector serves the launch: trgsw_ntt is a single TRGSW
+ * ((k+1)l (k+1) N doubles from cufhe_amd_trgsw_to_ntt_batch), not one per item as in cufhe_amd_cmux_batch -- an address bit acts on
+ * every TRLWE of a table.  res may be c.  Needs Initialize() only (the NTT tables), like cufhe_amd_cmux_batch. */
+int cufhe_amd_cmux_rotate_batch(int device, void* stream, size_t count, const double* trgsw_ntt, const int32_t* exps,
+                                const uint32_t* c, uint32_t* res);
+/* __SampleExtractIndex__<P,index> (src/bootstrap_gpu.cu:366-381) at a caller's index: tlwe1[g] = SampleExtract(idx[g])(trlwe[src[g]]),
+ * lvl1 TLWEs [count][N+1] with out[m] = a[j - m] (m <= j), -a[N + j - m] (m > j), out[N] = b[j]; 0 <= idx[g] < N.  src may be NULL
+ * (src[g] = g); several outputs may name one source.  src[g] must index a TRLWE of the caller's array: the ABI carries no length, so
+ * this is the caller's contract (a negative src[g] is refused).  The second form adds the key switch (SEIandKS,
+ * src/keyswitch_gpu.cu:26-40): tlwe0[count][n+1]; with idx all 0 and src NULL it is cufhe_amd_sample_extract_keyswitch_batch.  Only the
+ * second form uses the lvl1 -> lvl0 key: -3 before cufhe_amd_initialize. */
+int cufhe_amd_sample_extract_index_batch(int device, void* stream, size_t count, const uint32_t* trlwe, const int32_t* src,
+                                         const int32_t* idx, uint32_t* tlwe1);
+int cufhe_amd_sample_extract_index_keyswitch_batch(int device, void* stream, size_t count, const uint32_t* trlwe, const int32_t* src,
+                                                   const int32_t* idx, uint32_t* tlwe0);
 /* NTT product check of test/test_polynomial_mult_1024.cu: res = a * b negacyclic mod 2^32,
  * a signed with |a| <= 128 (exactness bound of the field), all [count][N], device. */
 int cufhe_amd_polymul_batch(int device, void* stream, size_t count, const int32_t* a,

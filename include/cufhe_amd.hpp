@@ -511,7 +511,30 @@ inline void SampleExtractAndKeySwitch(Ctxt<TFHEpp::lvl0param>& out, const cuFHET
     gSampleExtractAndKeySwitch(out, in, st);
     CUFHE_AMD_CHECK(cufhe_amd_enqueue_copy(st.device_id(), st.raw(), out.handle, 0));
 }
+/// SampleExtractAndKeySwitch at a caller's index (packed ROM words; __SampleExtractIndex__<P,index>,
+/// src/bootstrap_gpu.cu:366-381): out = KeySwitch(SampleExtract(index)(in)), 0 <= index < N.  No counterpart in the reference's host
+/// API, so the two forms follow the g-convention of the gates rather than the upload of the index-less pair above: the g-form reads
+/// and writes device buffers only (it follows gCMUXNTT / gCMUXRotateNTT without a copy), the other takes in.trlwehost and
+/// delivers out.tlwehost.  Default parameter set only.
+inline void gSampleExtractAndKeySwitch(Ctxt<TFHEpp::lvl0param>& out, const cuFHETRLWElvl1& in, int index, Stream st)
+{
+    CUFHE_AMD_CHECK(cufhe_amd_enqueue_trlwe_op(st.device_id(), st.raw(), CUFHE_AMD_TL_SEIKS_AT(index), 0, out.handle, in.handle));
+}
+inline void SampleExtractAndKeySwitch(Ctxt<TFHEpp::lvl0param>& out, const cuFHETRLWElvl1& in, int index, Stream st)
+{
+    CUFHE_AMD_CHECK(cufhe_amd_enqueue_trlwe_op(st.device_id(), st.raw(), CUFHE_AMD_TL_SEIKS_AT(index), 1, out.handle, in.handle));
+}
 #ifndef CUFHE_AMD_SMALL_NTT_MODULUS
+/// The rotating CMUX (packed ROM words): res = c + cs [x] (X^exponent c - c), 0 <= exponent < 2N -- CMUXNTT(res, cs, X^exponent c, c)
+/// without the rotated operand in memory; res may be c.  Recorded like CMUXNTT.  Default parameter set only.
+inline void CMUXRotateNTT(cuFHETRLWElvl1& res, cuFHETRGSWNTTlvl1& cs, cuFHETRLWElvl1& c, int exponent, Stream st)
+{
+    CUFHE_AMD_CHECK(cufhe_amd_enqueue_cmux_rotate(st.device_id(), st.raw(), 1, res.handle, cs.handle, c.handle, exponent));
+}
+inline void gCMUXRotateNTT(cuFHETRLWElvl1& res, cuFHETRGSWNTTlvl1& cs, cuFHETRLWElvl1& c, int exponent, Stream st)
+{
+    CUFHE_AMD_CHECK(cufhe_amd_enqueue_cmux_rotate(st.device_id(), st.raw(), 0, res.handle, cs.handle, c.handle, exponent));
+}
 /// CMUXNTT, src/cufhe_gates_gpu.cu:68-85: res = cs ? c1 : c0.  Like the reference it uploads cs, c1, c0 from their host
 /// members in stream order, returns at once, and res.trlwehost holds the result after Synchronize() / StreamQuery(st);
 /// operands that are results of earlier recorded operations are picked up by the scheduler's dependence tracking (no
