@@ -683,6 +683,13 @@ int launch_keyswitch_shared(DeviceState& s, hipStream_t st, const typename S::De
     hipLaunchKernelGGL(keyswitch_kernel<S>, dim3(ks_blocks), dim3(kKsThreads), KsDims<S>::lds_bytes, st, d, (int)count, ksk_padded, per_wg, slices);
     return 0;
 }
+// keyswitch_direct_kernel<S, SPLIT>: SPLIT workgroups per ciphertext, rows straight from L2; above one they add into a zeroed output
+template <class S, int SPLIT>
+void launch_keyswitch_direct(hipStream_t st, const typename S::Desc* d, size_t count, const uint32_t* ksk_padded)
+{
+    if (SPLIT > 1) hipLaunchKernelGGL(keyswitch_zero_kernel<S>, dim3((unsigned)count), dim3(256), 0, st, d, (int)count);
+    hipLaunchKernelGGL((keyswitch_direct_kernel<S, SPLIT>), dim3((unsigned)count * SPLIT), dim3(kKsThreads), 0, st, d, (int)count, ksk_padded);
+}
 int launch_keyswitch(DeviceState& s, hipStream_t st, const LinDesc* d, size_t count)
 {
     if (count == 0) return 0;
@@ -691,10 +698,9 @@ int launch_keyswitch(DeviceState& s, hipStream_t st, const LinDesc* d, size_t co
     const long split_max = g_ks_split_threshold < 0 ? ks_auto_split(cus_of(s)) : g_ks_split_threshold;
     const long wg_max = g_ks_wg_threshold < 0 ? ks_auto_wg(cus_of(s)) : g_ks_wg_threshold;
     if ((long)count <= split_max) {
-        hipLaunchKernelGGL(keyswitch_split_zero_kernel, dim3((unsigned)count), dim3(256), 0, st, d, (int)count);
-        hipLaunchKernelGGL(keyswitch_split_kernel, dim3((unsigned)count * kKsSplit), dim3(kKsThreads), 0, st, d, (int)count, s.ksk);
+        launch_keyswitch_direct<KsShapeDefault, kKsSplit>(st, d, count, s.ksk);
     } else if ((long)count <= wg_max) {
-        hipLaunchKernelGGL(keyswitch_wg_kernel, dim3((unsigned)count), dim3(kKsThreads), 0, st, d, (int)count, s.ksk);
+        launch_keyswitch_direct<KsShapeDefault, 1>(st, d, count, s.ksk);
     } else {
         if (int rc = launch_keyswitch_shared<KsShapeDefault>(s, st, d, count, s.ksk, &s.ks_lds_opt_in)) return rc;
     }

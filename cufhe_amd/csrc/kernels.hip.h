@@ -8,9 +8,9 @@
 //                                                   include/keyswitch_gpu.cuh:83-188
 //   lincomb_kernel         __NotBootstrap__/__CopyBootstrap__ and the Mux/NMux sums
 //                                                   src/bootstrap_gpu.cu:681-703,728-740
-//   keyswitch_wg_kernel / keyswitch_split_kernel   the key switch with one / eight workgroups per ciphertext (small launches;
-//                                                  the low-latency blind rotations are in kernels_ll.hip.h)
-//                                                   (small launches: lowest latency)
+//   keyswitch_direct_kernel                        the key switch with one / eight workgroups per ciphertext, rows straight from L2
+//                                                  (small launches: lowest latency; the low-latency blind rotations are in
+//                                                  kernels_ll.hip.h)
 //   sample_extract_kernel, cmux_kernel             SEIandKS / Refresh / CMUXNTT pieces
 //                                                   src/keyswitch_gpu.cu:26-40, src/bootstrap_gpu.cu:197-285
 //   sample_extract_index_kernel, trlwe_rotate_kernel, cmux_rotate_kernel
@@ -419,7 +419,7 @@ __global__ __launch_bounds__(kBrThreads, 2) void blind_rotate_kernel(
 constexpr int kKsWaves = 16;
 constexpr int kKsThreads = 64 * kKsWaves;                        // 1024
 constexpr int kKsRowPad = 640;                                   // words per padded row
-constexpr int kKsPieces = 3;                                     // 16-byte pieces per lane (the workgroup-per-ciphertext kernels)
+constexpr int kKsPieces = 3;                                     // 16-byte pieces per lane (keyswitch_direct_kernel)
 constexpr int kKsStepBytes = kKsT * kKsNumBase * kKsRowPad * 4;  // 40960: all rows of one j
 constexpr int kKsBuffers = 3;
 constexpr int kKsDigitSteps = 1024;                              // digit words a wave keeps in LDS: the steps of one workgroup
@@ -733,109 +733,34 @@ __global__ __launch_bounds__(kKsThreads) void keyswitch_kernel(
     if constexpr (K::pairs) { put(512 + 2 * lane, res[8]); put(513 + 2 * lane, res[9]); }
 }
 
-// Low-latency key switch: one workgroup (16 waves) per ciphertext, wave w takes the 64 values
-// a'_j, j in [64 w, 64 w + 64), reads its rows straight from L2 (eight rows in flight) and the
-// 16 partial sums are added through LDS.  Same words as keyswitch_kernel; used for small
-// launches, where sharing the table between ciphertexts buys nothing.
-__global__ __launch_bounds__(kKsThreads) void keyswitch_wg_kernel(
-    const LinDesc* __restrict__ descs, int count, const uint32_t* __restrict__ ksk_padded)
-{
-    __shared__ uint32_t part[kKsWaves][kKsRowPad];
-    __shared__ uint16_t dig[kN];
-    __shared__ uint32_t bprime_s;
-    const int g = blockIdx.x;
-    if (g >= count) return;
-    const int tid = threadIdx.x;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int lane = tid & 63;
-    const LinDesc d = descs[g];
-    uint32_t koff = 1u << (32 - (1 + kKsBasebit * kKsT));
-    for (int i = 1; i <= kKsT; i++) koff += ((1u << kKsBasebit) / 2) << (32 - i * kKsBasebit);
-    for (int j = tid; j < kLvl1Words; j += kKsThreads) {
-        const uint32_t v = (uint32_t)d.ca * d.in0[j] + (uint32_t)d.cb * d.in1[j];
-        if (j == kN) bprime_s = v + d.off;
-        else dig[j] = (uint16_t)((v + koff) >> 16);
-    }
-    __syncthreads();
-
-    int piece[kKsPieces];
-    piece[0] = lane; piece[1] = lane + 64; piece[2] = lane < 32 ? lane + 128 : 159;
-    uint4 res[kKsPieces];
-#pragma unroll
-    for (int m = 0; m < kKsPieces; m++) res[m] = make_uint4(0, 0, 0, 0);
-    const uint4* base = (const uint4*)ksk_padded;
-    constexpr int kRowPieces = kKsRowPad / 4;
-#pragma unroll 1
-    for (int jj = 0; jj < kN / kKsWaves; jj++) {
-        const int j = wave * (kN / kKsWaves) + jj;
-        const uint32_t dj = __builtin_amdgcn_readfirstlane((uint32_t)dig[j]);
-        int val[kKsT];
-        uint4 row[kKsT][kKsPieces];
-#pragma unroll
-        for (int k = 0; k < kKsT; k++) {
-            val[k] = (int)((dj >> (16 - (k + 1) * kKsBasebit)) & ((1u << kKsBasebit) - 1)) - (1 << (kKsBasebit - 1));
-            const int v = val[k] > 0 ? val[k] : -val[k];
-            const uint4* r = base + ((size_t)(j * kKsT + k) * kKsNumBase + (v ? v - 1 : 0)) * kRowPieces;
-#pragma unroll
-            for (int m = 0; m < kKsPieces; m++) row[k][m] = r[piece[m]];
-        }
-#pragma unroll
-        for (int k = 0; k < kKsT; k++) {
-            if (val[k] > 0) {
-#pragma unroll
-                for (int m = 0; m < kKsPieces; m++) { res[m].x -= row[k][m].x; res[m].y -= row[k][m].y; res[m].z -= row[k][m].z; res[m].w -= row[k][m].w; }
-            } else if (val[k] < 0) {
-#pragma unroll
-                for (int m = 0; m < kKsPieces; m++) { res[m].x += row[k][m].x; res[m].y += row[k][m].y; res[m].z += row[k][m].z; res[m].w += row[k][m].w; }
-            }
-        }
-    }
-#pragma unroll
-    for (int m = 0; m < kKsPieces; m++) {
-        if (m == 2 && lane >= 32) break;
-        *(uint4*)&part[wave][4 * piece[m]] = res[m];
-    }
-    __syncthreads();
-    for (int i = tid; i <= kLvl0N; i += kKsThreads) {
-        uint32_t v = (i == kLvl0N) ? bprime_s : 0u;
-#pragma unroll
-        for (int w = 0; w < kKsWaves; w++) v += part[w][i];
-        d.out[i] = v;
-    }
-}
-
-// Lowest-latency key switch for a handful of ciphertexts: kKsSplit workgroups per ciphertext, each
-// taking 128 values of j (8 per wave) and adding its partial sum into the output with 32-bit
-// atomics (sums mod 2^32 are order-free: same words).  The output is zeroed by
-// keyswitch_split_zero_kernel first; the workgroup of j = 0 adds b'.
+// The direct key switch: SPLIT workgroups (16 waves each) per ciphertext, no table sharing.  Workgroup i serves ciphertext
+// i / SPLIT and the J = kn / SPLIT values a'_j from (i % SPLIT) * J on; wave w takes J / 16 consecutive ones, reads their rows
+// straight from L2 (the rows of all t digits in flight together) and the 16 partial sums are added through LDS.  SPLIT == 1
+// stores the result; otherwise it is added into the output with 32-bit atomics (sums mod 2^32 are order-free: same words),
+// which keyswitch_zero_kernel<S> has zeroed first, and the workgroup of j = 0 adds b'.  Same words as keyswitch_kernel; for
+// small launches, where sharing the table between ciphertexts buys nothing: kKsSplit workgroups per ciphertext is the lowest
+// latency for a handful of them (profiles/r06_keyswitch.md).
 constexpr int kKsSplit = 8;
-__global__ __launch_bounds__(256) void keyswitch_split_zero_kernel(const LinDesc* __restrict__ descs, int count)
+template <class S, int SPLIT>
+__global__ __launch_bounds__(kKsThreads) void keyswitch_direct_kernel(
+    const typename S::Desc* __restrict__ descs, int count, const uint32_t* __restrict__ ksk_padded)
 {
-    const int g = blockIdx.x;
-    if (g >= count) return;
-    uint32_t* out = descs[g].out;
-    for (int i = threadIdx.x; i <= kLvl0N; i += blockDim.x) out[i] = 0u;
-}
-__global__ __launch_bounds__(kKsThreads) void keyswitch_split_kernel(
-    const LinDesc* __restrict__ descs, int count, const uint32_t* __restrict__ ksk_padded)
-{
+    static_assert(S::row_pad == kKsRowPad && S::n_out < kKsRowPad, "a lane's third piece (lane + 128, lanes 0..31) ends a row of 640 words");
+    static_assert(S::kn % (SPLIT * kKsWaves) == 0, "every wave of every workgroup takes the same number of values a'_j");
+    static_assert(S::t * kKsBasebit <= 16, "digit word of 16 bits");
+    constexpr int J = S::kn / SPLIT;                           // values of j per workgroup
     __shared__ uint32_t part[kKsWaves][kKsRowPad];
-    __shared__ uint16_t dig[kN / kKsSplit];
-    const int g = blockIdx.x / kKsSplit, sp = blockIdx.x % kKsSplit;
+    __shared__ uint16_t dig[J];
+    const int g = blockIdx.x / SPLIT, sp = blockIdx.x % SPLIT;
     if (g >= count) return;
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lane = tid & 63;
-    const LinDesc d = descs[g];
-    uint32_t koff = 1u << (32 - (1 + kKsBasebit * kKsT));
-    for (int i = 1; i <= kKsT; i++) koff += ((1u << kKsBasebit) / 2) << (32 - i * kKsBasebit);
-    constexpr int kJ = kN / kKsSplit;                          // 128 values of j per workgroup
-    const int j0 = sp * kJ;
-    if (tid < kJ) {
-        const uint32_t v = (uint32_t)d.ca * d.in0[j0 + tid] + (uint32_t)d.cb * d.in1[j0 + tid];
-        dig[tid] = (uint16_t)((v + koff) >> 16);
-    }
+    const typename S::Desc d = descs[g];
+    const int j0 = sp * J;
+    for (int jl = tid; jl < J; jl += kKsThreads) dig[jl] = (uint16_t)S::digit_word(d, j0 + jl);
     __syncthreads();
+
     int piece[kKsPieces];
     piece[0] = lane; piece[1] = lane + 64; piece[2] = lane < 32 ? lane + 128 : 159;
     uint4 res[kKsPieces];
@@ -844,22 +769,22 @@ __global__ __launch_bounds__(kKsThreads) void keyswitch_split_kernel(
     const uint4* base = (const uint4*)ksk_padded;
     constexpr int kRowPieces = kKsRowPad / 4;
 #pragma unroll 1
-    for (int jj = 0; jj < kJ / kKsWaves; jj++) {
-        const int jl = wave * (kJ / kKsWaves) + jj;
+    for (int jj = 0; jj < J / kKsWaves; jj++) {
+        const int jl = wave * (J / kKsWaves) + jj;
         const int j = j0 + jl;
         const uint32_t dj = __builtin_amdgcn_readfirstlane((uint32_t)dig[jl]);
-        int val[kKsT];
-        uint4 row[kKsT][kKsPieces];
+        int val[S::t];
+        uint4 row[S::t][kKsPieces];
 #pragma unroll
-        for (int k = 0; k < kKsT; k++) {
-            val[k] = (int)((dj >> (16 - (k + 1) * kKsBasebit)) & ((1u << kKsBasebit) - 1)) - (1 << (kKsBasebit - 1));
+        for (int k = 0; k < S::t; k++) {
+            val[k] = (int)ks_field(dj, k) - (1 << (kKsBasebit - 1));
             const int v = val[k] > 0 ? val[k] : -val[k];
-            const uint4* r = base + ((size_t)(j * kKsT + k) * kKsNumBase + (v ? v - 1 : 0)) * kRowPieces;
+            const uint4* r = base + ((size_t)(j * S::t + k) * kKsNumBase + (v ? v - 1 : 0)) * kRowPieces;    // digit 0: a harmless row
 #pragma unroll
             for (int m = 0; m < kKsPieces; m++) row[k][m] = r[piece[m]];
         }
 #pragma unroll
-        for (int k = 0; k < kKsT; k++) {
+        for (int k = 0; k < S::t; k++) {
             if (val[k] > 0) {
 #pragma unroll
                 for (int m = 0; m < kKsPieces; m++) { res[m].x -= row[k][m].x; res[m].y -= row[k][m].y; res[m].z -= row[k][m].z; res[m].w -= row[k][m].w; }
@@ -875,12 +800,13 @@ __global__ __launch_bounds__(kKsThreads) void keyswitch_split_kernel(
         *(uint4*)&part[wave][4 * piece[m]] = res[m];
     }
     __syncthreads();
-    for (int i = tid; i <= kLvl0N; i += kKsThreads) {
-        uint32_t v = 0u;
-        if (i == kLvl0N && sp == 0) v = (uint32_t)d.ca * d.in0[kN] + (uint32_t)d.cb * d.in1[kN] + d.off;
+    uint32_t* o = d.out;                                     // 4-byte aligned only (ciphertexts packed at n_out + 1 words)
+    for (int i = tid; i <= S::n_out; i += kKsThreads) {
+        uint32_t v = (i == S::n_out && sp == 0) ? S::bprime(d) : 0u;
 #pragma unroll
         for (int w = 0; w < kKsWaves; w++) v += part[w][i];
-        atomicAdd(d.out + i, v);
+        if constexpr (SPLIT == 1) o[i] = v;
+        else atomicAdd(o + i, v);
     }
 }
 

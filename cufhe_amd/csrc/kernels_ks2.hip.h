@@ -9,7 +9,8 @@ namespace cufhe_amd {
 // The lvl20 key switch with the table shared through LDS: keyswitch_kernel (kernels.hip.h) over the lvl20 shape -- 2048 values
 // a'_j of 64 bits per ciphertext, t = 7 digits each, 14 candidate rows of 640 words per j (35 KiB contiguous in the padded layout).
 // A workgroup keeps the digit words of at most 1024 steps, so a launch always cuts j into at least two runs (KsDims::min_slices).
-// L2 traffic drops 16x against keyswitch_lvl2_kernel (a workgroup per ciphertext, rows straight from L2).
+// L2 traffic drops 16x against keyswitch_direct_kernel<KsShapeLvl2, 1> (a workgroup per ciphertext, wave w takes a'_j for j in
+// [128 w, 128 w + 128), rows straight from L2).
 // ----------------------------------------------------------------------------------
 struct KsShapeLvl2 {
     using Desc = LinDesc64;

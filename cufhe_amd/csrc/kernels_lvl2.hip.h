@@ -568,78 +568,10 @@ __global__ __launch_bounds__(k2Threads) void blind_rotate_lvl2_kernel(
 
 // ----------------------------------------------------------------------------------
 // Key switch lvl2 -> lvl0 (KeySwitchFromTLWE<lvl20>, include/keyswitch_gpu.cuh:83-134) with
-// the linear pre-add of the Mux fused.  One workgroup (16 waves) per ciphertext, wave w takes
-// a'_j for j in [128 w, 128 w + 128); rows are read from L2, the 16 partial sums are added
-// through LDS.  Table layout as lvl1: [j][k][v][640] padded rows.
+// the linear pre-add of the Mux fused: keyswitch_kernel and keyswitch_direct_kernel
+// (kernels.hip.h) over KsShapeLvl2 (kernels_ks2.hip.h).  Table layout as lvl1:
+// [j][k][v][640] padded rows.
 // ----------------------------------------------------------------------------------
 constexpr int k2KsStepRows = k2KsT * k2KsNumBase;             // 14 rows per j
-
-__global__ __launch_bounds__(kKsThreads) void keyswitch_lvl2_kernel(
-    const LinDesc64* __restrict__ descs, int count, const uint32_t* __restrict__ ksk_padded)
-{
-    __shared__ uint32_t part[kKsWaves][kKsRowPad];
-    __shared__ uint16_t dig[k2N];
-    __shared__ uint32_t bprime_s;
-    const int g = blockIdx.x;
-    if (g >= count) return;
-    const int tid = threadIdx.x;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int lane = tid & 63;
-    const LinDesc64 d = descs[g];
-    // iksoffsetgen<lvl20> + roundoffset (:13-23,92-98); only the top t*basebit = 14 bits carry digits
-    uint64_t koff = 1ull << (64 - (1 + k2KsBasebit * k2KsT));
-    for (int i = 1; i <= k2KsT; i++) koff += ((1ull << k2KsBasebit) / 2) << (64 - i * k2KsBasebit);
-    for (int j = tid; j < k2Words; j += kKsThreads) {
-        const uint64_t v = (uint64_t)(int64_t)d.ca * d.in0[j] + (uint64_t)(int64_t)d.cb * d.in1[j];
-        if (j == k2N) bprime_s = (uint32_t)((v + d.off + (1ull << 31)) >> 32);     // rounding narrowing, :100-101
-        else dig[j] = (uint16_t)((v + koff) >> 48);
-    }
-    __syncthreads();
-
-    int piece[kKsPieces];
-    piece[0] = lane; piece[1] = lane + 64; piece[2] = lane < 32 ? lane + 128 : 159;
-    uint4 res[kKsPieces];
-#pragma unroll
-    for (int m = 0; m < kKsPieces; m++) res[m] = make_uint4(0, 0, 0, 0);
-    const uint4* base = (const uint4*)ksk_padded;
-    constexpr int kRowPieces = kKsRowPad / 4;
-#pragma unroll 1
-    for (int jj = 0; jj < k2N / kKsWaves; jj++) {
-        const int j = wave * (k2N / kKsWaves) + jj;
-        const uint32_t dj = __builtin_amdgcn_readfirstlane((uint32_t)dig[j]);
-        int val[k2KsT];
-        uint4 row[k2KsT][kKsPieces];
-#pragma unroll
-        for (int k = 0; k < k2KsT; k++) {
-            val[k] = (int)((dj >> (16 - (k + 1) * k2KsBasebit)) & ((1u << k2KsBasebit) - 1)) - (1 << (k2KsBasebit - 1));
-            const int v = val[k] > 0 ? val[k] : -val[k];
-            const uint4* r = base + ((size_t)(j * k2KsT + k) * k2KsNumBase + (v ? v - 1 : 0)) * kRowPieces;
-#pragma unroll
-            for (int m = 0; m < kKsPieces; m++) row[k][m] = r[piece[m]];
-        }
-#pragma unroll
-        for (int k = 0; k < k2KsT; k++) {
-            if (val[k] > 0) {
-#pragma unroll
-                for (int m = 0; m < kKsPieces; m++) { res[m].x -= row[k][m].x; res[m].y -= row[k][m].y; res[m].z -= row[k][m].z; res[m].w -= row[k][m].w; }
-            } else if (val[k] < 0) {
-#pragma unroll
-                for (int m = 0; m < kKsPieces; m++) { res[m].x += row[k][m].x; res[m].y += row[k][m].y; res[m].z += row[k][m].z; res[m].w += row[k][m].w; }
-            }
-        }
-    }
-#pragma unroll
-    for (int m = 0; m < kKsPieces; m++) {
-        if (m == 2 && lane >= 32) break;
-        *(uint4*)&part[wave][4 * piece[m]] = res[m];
-    }
-    __syncthreads();
-    for (int i = tid; i <= kLvl0N; i += kKsThreads) {
-        uint32_t v = (i == kLvl0N) ? bprime_s : 0u;
-#pragma unroll
-        for (int w = 0; w < kKsWaves; w++) v += part[w][i];
-        d.out[i] = v;
-    }
-}
 
 }  // namespace cufhe_amd

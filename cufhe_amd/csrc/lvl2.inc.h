@@ -134,10 +134,10 @@ int launch_keyswitch_lvl2(DeviceState& s, hipStream_t st, const LinDesc64* d, si
     if (count == 0) return 0;
     ProfScope prof{s, st, count, true};
     if (int rc = prof.begin()) return rc;
-    // keyswitch_kernel over the lvl20 shape (j cut into runs that fill the CUs) at any count; the workgroup-per-ciphertext kernel
-    // (2.1 us per ciphertext) only by "ks_wg_threshold"
+    // keyswitch_kernel over the lvl20 shape (j cut into runs that fill the CUs) at any count; keyswitch_direct_kernel with a
+    // workgroup per ciphertext (2.1 us per ciphertext) only by "ks_wg_threshold"
     if (g_ks_wg_threshold > 0 && (long)count <= g_ks_wg_threshold) {
-        hipLaunchKernelGGL(keyswitch_lvl2_kernel, dim3((unsigned)count), dim3(kKsThreads), 0, st, d, (int)count, s.ksk2);
+        launch_keyswitch_direct<KsShapeLvl2, 1>(st, d, count, s.ksk2);
     } else {
         if (int rc = launch_keyswitch_shared<KsShapeLvl2>(s, st, d, count, s.ksk2, &s.ks2_lds_opt_in)) return rc;
     }

@@ -146,7 +146,8 @@ def test_keyswitch_words(engine, keys, oracle, br_kernel):
 def test_keyswitch_shared_table_groupings(engine, keys, oracle, count):
     """The shared-table key switch (the ciphertexts of a workgroup share each step of the key through LDS, a wave per ciphertext):
     odd counts, a last workgroup that is not full, the largest and the smallest number of ciphertexts per workgroup -- every word
-    equal to the workgroup-per-ciphertext kernel's, first and last ciphertext equal to the oracle's."""
+    equal to the workgroup-per-ciphertext kernel's, first and last ciphertext equal to the oracle's.  The eight-workgroup form of the
+    direct kernel (the default of small launches) gives the same words at every count."""
     rng = np.random.default_rng(4100 + count)
     t1 = rng.integers(0, 2**32, size=(count, ol.N + 1), dtype=np.uint64).astype(np.uint32)
     t1[0, : ol.N] = 0xFFFFFFFF
@@ -171,6 +172,7 @@ def test_keyswitch_shared_table_groupings(engine, keys, oracle, count):
         want = np.zeros(ol.n + 1, np.uint32)
         oracle.orc_keyswitch(keys.ek, want, np.ascontiguousarray(t1[g]))
         assert np.array_equal(ref[g], want)
+    assert np.array_equal(run(1 << 30, 0, -1), ref), f"eight workgroups per ciphertext, {count} ciphertexts"
     # (ciphertexts per workgroup, runs the steps of j are cut into: above one the partial sums meet in the output through atomics)
     for per, slices in ((-1, -1), (1, 1), (6, 1), (16, 1), (16, 2), (9, 4), (-1, 16), (16, 64)):
         got = run(0, 0, per, slices)
