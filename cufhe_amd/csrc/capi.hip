@@ -166,179 +166,6 @@ std::deque<DeviceState> g_dev(1);    // re-created only while no device is initi
 int cus_of(const DeviceState& s) { return g_cus_override > 0 ? (int)g_cus_override : s.cus; }
 std::mutex g_mu;
 
-// ---- exact host arithmetic for the tables ----
-typedef unsigned __int128 u128;
-uint64_t mulmod_u64(uint64_t a, uint64_t b) { return (uint64_t)((u128)a * b % fpf::P_U64); }
-uint64_t powmod_u64(uint64_t a, uint64_t e)
-{
-    uint64_t r = 1;
-    while (e) {
-        if (e & 1) r = mulmod_u64(r, a);
-        a = mulmod_u64(a, a);
-        e >>= 1;
-    }
-    return r;
-}
-double balanced(uint64_t v) { return v > fpf::P_U64 / 2 ? -(double)(fpf::P_U64 - v) : (double)v; }
-uint32_t bitrev(uint32_t x, int bits)
-{
-    uint32_t r = 0;
-    for (int i = 0; i < bits; i++) r |= ((x >> i) & 1u) << (bits - 1 - i);
-    return r;
-}
-double n_inverse_balanced() { return balanced(powmod_u64(kN, fpf::P_U64 - 2)); }
-
-// Device tables of one 1024-point transform from its root arrays, fwd[m + g] / inv[m + g]
-// being the twiddle of group g at the stage with m groups.
-// r4: the tables of the radix-4 passes (ntt_r4.h).  A 16-register block uses the twiddles [w | u, I u | w_0..w_3 | u_0, I u_0, ..];
-// the radix-4 butterfly never multiplies by the second twiddle of a fine pair (root[2m + 1] = I root[2m], -I for the inverse)
-// but by the product of the first with the coarse twiddle: slot 2 = u w, slot 8 + 2g = u_g w_g (tc: slot 5 + 2g = u_g w_g).
-double mul_balanced(double a, double b)
-{
-    const uint64_t ua = a < 0 ? fpf::P_U64 - (uint64_t)(-a) : (uint64_t)a, ub = b < 0 ? fpf::P_U64 - (uint64_t)(-b) : (uint64_t)b;
-    return balanced(mulmod_u64(ua, ub));
-}
-void to_r4_block(double* t, int stride)       // t[k * stride], k < 15: one block of four stages
-{
-    t[2 * stride] = mul_balanced(t[1 * stride], t[0]);
-    for (int g = 0; g < 4; g++) t[(8 + 2 * g) * stride] = mul_balanced(t[(7 + 2 * g) * stride], t[(3 + g) * stride]);
-}
-void fill_tables(NttTables& t, const std::vector<double>& fwd, const std::vector<double>& inv, bool r4 = false)
-{
-    memset(&t, 0, sizeof(t));
-    for (int k = 0; k < 15; k++) {
-        int lvl = 0;
-        while ((2 << lvl) <= k + 1) lvl++;
-        const int j = k + 1 - (1 << lvl);
-        t.tu_fwd[k] = fwd[(1 << lvl) + j];
-        t.tu_inv[k] = inv[(1 << lvl) + j];
-        for (int lam = 0; lam < 16; lam++) {
-            const int idx = (16 << lvl) + (lam << lvl) + j;
-            t.tb_fwd[k * 16 + lam] = fwd[idx];
-            t.tb_inv[k * 16 + lam] = inv[idx];
-        }
-    }
-    for (int k = 0; k < kTcCount; k++)
-        for (int lane = 0; lane < 64; lane++) {
-            const int lam = lane & 15, h = lane >> 4;
-            const int idx = k < 4 ? 256 + ((lam << 4) | (h << 2) | k) : 512 + ((lam << 5) | (h << 3) | (k - 4));
-            t.tc_fwd[k * 64 + lane] = fwd[idx];
-            t.tc_inv[k * 64 + lane] = inv[idx];
-        }
-    if (r4) {
-        to_r4_block(t.tu_fwd, 1);
-        to_r4_block(t.tu_inv, 1);
-        for (int lam = 0; lam < 16; lam++) {
-            to_r4_block(t.tb_fwd + lam, 16);
-            to_r4_block(t.tb_inv + lam, 16);
-        }
-        for (int lane = 0; lane < 64; lane++)
-            for (int g = 0; g < 4; g++) {
-                t.tc_fwd[(5 + 2 * g) * 64 + lane] = mul_balanced(t.tc_fwd[(4 + 2 * g) * 64 + lane], t.tc_fwd[g * 64 + lane]);
-                t.tc_inv[(5 + 2 * g) * 64 + lane] = mul_balanced(t.tc_inv[(4 + 2 * g) * 64 + lane], t.tc_inv[g * 64 + lane]);
-            }
-        // packed per lane (ntt_wave.h: NttTables::tbp_fwd ..)
-        for (int lam = 0; lam < 16; lam++)
-            for (int k = 0; k < kTbCount; k++) {
-                t.tbp_fwd[lam * kTbpStride + k] = t.tb_fwd[k * 16 + lam];
-                t.tbp_inv[lam * kTbpStride + k] = t.tb_inv[k * 16 + lam];
-            }
-        for (int lane = 0; lane < 64; lane++)
-            for (int k = 0; k < kTcCount; k++) {
-                t.tcp_fwd[lane * kTcpStride + k] = t.tc_fwd[k * 64 + lane];
-                t.tcp_inv[lane * kTcpStride + k] = t.tc_inv[k * 64 + lane];
-            }
-    }
-}
-
-// root[i] = psi^bitrev(i): the reference's table order, src/ntt_gpu/ntt_gpuntt.cu:88-111
-void build_tables(NttTables& t, bool r4 = false)
-{
-    std::vector<double> fwd(kN), inv(kN);
-    const uint64_t psi = fpf::PSI_2048, psi_inv = powmod_u64(psi, fpf::P_U64 - 2);
-    for (uint32_t i = 0; i < (uint32_t)kN; i++) {
-        fwd[i] = balanced(powmod_u64(psi, bitrev(i, 10)));
-        inv[i] = balanced(powmod_u64(psi_inv, bitrev(i, 10)));
-    }
-    fill_tables(t, fwd, inv, r4);
-}
-
-// exact product mod p of two balanced residues held in doubles, balanced again
-double prod_balanced(double a, double b)
-{
-    const __int128 p = (__int128)fpf::P_U64;
-    __int128 v = ((__int128)(int64_t)a * (__int128)(int64_t)b) % p;
-    if (v < 0) v += p;
-    return balanced((uint64_t)v);
-}
-
-// Radix-4 form of a 512-point transform (ntt_wave512.h: q4): the product of a block's stage-a and first stage-b twiddle, u w
-// (forward) and v w (inverse) -- in the spare slot 7 of tu_fwd / tu_inv for the wave-uniform block, in uwb_* / uwc_* per lam and per
-// lane.  The second stage-b twiddle must be I times (forward) / -I times (inverse) the first: false if it is not.
-bool fill_r4_products_512(Ntt512Tables& t)
-{
-    auto apart = [&](double w1, double w2, bool inverse) { return prod_balanced(w1, inverse ? -fpf::ROOT4 : fpf::ROOT4) == w2; };
-    if (!apart(t.tu_fwd[1], t.tu_fwd[2], false) || !apart(t.tu_inv[1], t.tu_inv[2], true)) return false;
-    t.tu_fwd[7] = prod_balanced(t.tu_fwd[0], t.tu_fwd[1]);
-    t.tu_inv[7] = prod_balanced(t.tu_inv[0], t.tu_inv[1]);
-    for (int lam = 0; lam < 8; lam++) {
-        if (!apart(t.tb_fwd[8 + lam], t.tb_fwd[16 + lam], false) || !apart(t.tb_inv[8 + lam], t.tb_inv[16 + lam], true)) return false;
-        t.uwb_fwd[lam] = prod_balanced(t.tb_fwd[lam], t.tb_fwd[8 + lam]);
-        t.uwb_inv[lam] = prod_balanced(t.tb_inv[lam], t.tb_inv[8 + lam]);
-    }
-    for (int lane = 0; lane < 64; lane++) {
-        if (!apart(t.tc_fwd[64 + lane], t.tc_fwd[128 + lane], false) || !apart(t.tc_inv[64 + lane], t.tc_inv[128 + lane], true)) return false;
-        t.uwc_fwd[lane] = prod_balanced(t.tc_fwd[lane], t.tc_fwd[64 + lane]);
-        t.uwc_inv[lane] = prod_balanced(t.tc_inv[lane], t.tc_inv[64 + lane]);
-    }
-    return true;
-}
-
-// Tables of one 512-point transform from accessors rf(idx) / ri(idx) = forward / inverse twiddle of
-// group g at the stage with m groups, idx = m + g.
-template <class RF, class RI>
-void fill_tables_512(Ntt512Tables& t, RF rf, RI ri)
-{
-    memset(&t, 0, sizeof(t));
-    for (int k = 0; k < 7; k++) {
-        int lvl = 0;
-        while ((2 << lvl) <= k + 1) lvl++;
-        const int j = k + 1 - (1 << lvl);
-        t.tu_fwd[k] = rf((1 << lvl) + j);
-        t.tu_inv[k] = ri((1 << lvl) + j);
-        for (int lam = 0; lam < 8; lam++) {
-            const int idx = (8 << lvl) + (lam << lvl) + j;
-            t.tb_fwd[k * 8 + lam] = rf(idx);
-            t.tb_inv[k * 8 + lam] = ri(idx);
-        }
-        for (int lane = 0; lane < 64; lane++) {
-            const int mu = 8 * (lane & 7) + (lane >> 3);
-            const int idx = (64 << lvl) + (mu << lvl) + j;
-            t.tc_fwd[k * 64 + lane] = rf(idx);
-            t.tc_inv[k * 64 + lane] = ri(idx);
-        }
-    }
-}
-
-// t[0], t[1]: the two 512-point halves of the 1024-point transform, root_h[m + g] = root[2m + h m + g];
-// t[2]: the stand-alone 512-point negacyclic transform (psi_1024 = psi_2048^2)
-void build_tables_512(Ntt512Tables (&t)[3])
-{
-    std::vector<double> fwd(kN), inv(kN);
-    const uint64_t psi = fpf::PSI_2048, psi_inv = powmod_u64(psi, fpf::P_U64 - 2);
-    for (uint32_t i = 0; i < (uint32_t)kN; i++) {
-        fwd[i] = balanced(powmod_u64(psi, bitrev(i, 10)));
-        inv[i] = balanced(powmod_u64(psi_inv, bitrev(i, 10)));
-    }
-    auto top = [](int idx) { int m = 1; while (2 * m <= idx) m *= 2; return m; };
-    for (int h = 0; h < 2; h++)
-        fill_tables_512(t[h], [&](int idx) { const int m = top(idx); return fwd[2 * m + h * m + (idx - m)]; },
-                        [&](int idx) { const int m = top(idx); return inv[2 * m + h * m + (idx - m)]; });
-    const uint64_t psi2 = mulmod_u64(psi, psi), psi2_inv = powmod_u64(psi2, fpf::P_U64 - 2);
-    fill_tables_512(t[2], [&](int idx) { return balanced(powmod_u64(psi2, bitrev((uint32_t)idx, 9))); },
-                    [&](int idx) { return balanced(powmod_u64(psi2_inv, bitrev((uint32_t)idx, 9))); });
-}
-
 // /sys/bus/pci/devices/<domain:bus:dev.fn>/local_cpulist of a physical HIP device ("" when it cannot be read)
 std::string device_local_cpulist(int phys)
 {
@@ -380,16 +207,22 @@ int use_device(int device)
     return 0;
 }
 
+// DeviceState::cus of a logical device
+int read_cus(DeviceState& s, int device)
+{
+    hipDeviceProp_t prop;
+    HIP_TRY(hipGetDeviceProperties(&prop, phys_device(device)));
+    s.cus = prop.multiProcessorCount;
+    return 0;
+}
+
+// twiddle tables: built by ntt_tables.h (host-only, checked on the CPU by tests/test_ntt_tables.py), uploaded here
 int ensure_ntt(int device)
 {
     DeviceState& s = g_dev[device];
     if (s.ntt_ready) return 0;
     HIP_TRY(hipSetDevice(phys_device(device)));
-    {
-        hipDeviceProp_t prop;
-        HIP_TRY(hipGetDeviceProperties(&prop, phys_device(device)));
-        s.cus = prop.multiProcessorCount;
-    }
+    if (int rc = read_cus(s, device)) return rc;
     // every allocation of this function is released again when a later one fails: a retry starts from nothing
     auto undo = [&]() {
         if (s.fault_host) { (void)hipHostFree(s.fault_host); s.fault_host = nullptr; s.fault = nullptr; }
@@ -1358,7 +1191,7 @@ int cufhe_amd_initialize(const uint32_t* bk, size_t bk_words, const uint32_t* ks
         const size_t polys = want_bk / kN;
         const unsigned blocks = (unsigned)((polys + kNttWavesPerBlock - 1) / kNttWavesPerBlock);
         hipLaunchKernelGGL(bk_to_ntt_kernel, dim3(blocks), dim3(kNttThreads), kNttLdsBytes, 0, b.bk_ntt.p, b.d_bk.p,
-                           polys, s.tables, n_inverse_balanced());
+                           polys, s.tables, n_inverse(kN));
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipDeviceSynchronize());        // also: nothing on this device still reads the keys that are about to go
     }
@@ -1684,7 +1517,7 @@ int cufhe_amd_trgsw_to_ntt_batch(int device, void* stream, size_t count, const u
     const size_t polys = count * kBkPolysPerStep;
     const unsigned blocks = (unsigned)((polys + kNttWavesPerBlock - 1) / kNttWavesPerBlock);
     hipLaunchKernelGGL(bk_to_ntt_kernel, dim3(blocks), dim3(kNttThreads), kNttLdsBytes, (hipStream_t)stream, trgsw_ntt,
-                       trgsw, polys, g_dev[device].tables, n_inverse_balanced());
+                       trgsw, polys, g_dev[device].tables, n_inverse(kN));
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1718,7 +1551,7 @@ int cufhe_amd_trgsw_to_ntt_host(int device, void* stream, const uint32_t* trgsw_
     HIP_TRY(hipMemcpyAsync(d_in, blk->host, in_bytes, hipMemcpyHostToDevice, st));
     const unsigned blocks = (unsigned)((kBkPolysPerStep + kNttWavesPerBlock - 1) / kNttWavesPerBlock);
     hipLaunchKernelGGL(bk_to_ntt_kernel, dim3(blocks), dim3(kNttThreads), kNttLdsBytes, st, d_out, d_in, (size_t)kBkPolysPerStep,
-                       s.tables, n_inverse_balanced());
+                       s.tables, n_inverse(kN));
     HIP_TRY(hipGetLastError());
     char* pin_out = (char*)blk->host + in_bytes;
     HIP_TRY(hipMemcpyAsync(pin_out, d_out, out_bytes, hipMemcpyDeviceToHost, st));
@@ -1923,7 +1756,7 @@ int cufhe_amd_polymul_batch(int device, void* stream, size_t count, const int32_
     if (count == 0) return 0;
     const unsigned blocks = (unsigned)((count + kNttWavesPerBlock - 1) / kNttWavesPerBlock);
     hipLaunchKernelGGL(polymul_kernel, dim3(blocks), dim3(kNttThreads), kNttLdsBytes, (hipStream_t)stream, res, a, b,
-                       (int)count, g_dev[device].tables, n_inverse_balanced());
+                       (int)count, g_dev[device].tables, n_inverse(kN));
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1938,7 +1771,7 @@ int cufhe_amd_polymul512_batch(int device, void* stream, size_t count, const int
     if (count == 0) return 0;
     const unsigned blocks = (unsigned)((count + kNttWavesPerBlock - 1) / kNttWavesPerBlock);
     hipLaunchKernelGGL(polymul512_kernel, dim3(blocks), dim3(kNttThreads), kPoly512LdsBytes, (hipStream_t)stream, res, a, b,
-                       (int)count, g_dev[device].tables512 + 2, balanced(powmod_u64(kH, fpf::P_U64 - 2)));
+                       (int)count, g_dev[device].tables512 + 2, n_inverse(kH));
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -54,7 +54,7 @@ int cb_to_ntt(DeviceState& s, hipStream_t st, size_t count, const uint32_t* trgs
     const size_t polys = count * kBkPolysPerStep;
     const unsigned blocks = (unsigned)((polys + kNttWavesPerBlock - 1) / kNttWavesPerBlock);
     hipLaunchKernelGGL(bk_to_ntt_kernel, dim3(blocks), dim3(kNttThreads), kNttLdsBytes, st, trgsw_ntt, trgsw, polys, s.tables,
-                       n_inverse_balanced());
+                       n_inverse(kN));
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -6,53 +6,13 @@
 
 namespace {
 
-constexpr uint64_t kPsi4096 = 245080461804091ull;     // psi^2 = PSI_2048, psi^1024 = ROOT4
-
-// Tables of the two half transforms: root_h[m + g] = root[2m + h m + g], root[i] = psi^bitrev11(i)
-void build_tables_lvl2(NttTables (&t)[2])
-{
-    std::vector<double> R(k2N), Rinv(k2N);
-    const uint64_t psi_inv = powmod_u64(kPsi4096, fpf::P_U64 - 2);
-    for (uint32_t i = 0; i < (uint32_t)k2N; i++) {
-        R[i] = balanced(powmod_u64(kPsi4096, bitrev(i, k2Nbit)));
-        Rinv[i] = balanced(powmod_u64(psi_inv, bitrev(i, k2Nbit)));
-    }
-    for (int h = 0; h < 2; h++) {
-        std::vector<double> fwd(kN, 0.0), inv(kN, 0.0);
-        for (int m = 1; m < kN; m <<= 1)
-            for (int g = 0; g < m; g++) {
-                fwd[m + g] = R[2 * m + h * m + g];
-                inv[m + g] = Rinv[2 * m + h * m + g];
-            }
-        fill_tables(t[h], fwd, inv);
-    }
-}
-
-// Tables of the four quarter transforms (kernels_lvl2q.hip.h): root_q[m + g] = root[4m + q m + g]
-void build_tables_lvl2q(Ntt512Tables (&t)[4])
-{
-    std::vector<double> R(k2N), Rinv(k2N);
-    const uint64_t psi_inv = powmod_u64(kPsi4096, fpf::P_U64 - 2);
-    for (uint32_t i = 0; i < (uint32_t)k2N; i++) {
-        R[i] = balanced(powmod_u64(kPsi4096, bitrev(i, k2Nbit)));
-        Rinv[i] = balanced(powmod_u64(psi_inv, bitrev(i, k2Nbit)));
-    }
-    auto top = [](int idx) { int m = 1; while (2 * m <= idx) m *= 2; return m; };
-    for (int q = 0; q < 4; q++)
-        fill_tables_512(t[q], [&](int idx) { const int m = top(idx); return R[4 * m + q * m + (idx - m)]; },
-                        [&](int idx) { const int m = top(idx); return Rinv[4 * m + q * m + (idx - m)]; });
-}
-
 int ensure_tables_lvl2(int device)
 {
     DeviceState& s = g_dev[device];
     if (s.tables2 && s.tables2q) return 0;
     HIP_TRY(hipSetDevice(phys_device(device)));
-    if (!s.cus) {
-        hipDeviceProp_t prop;
-        HIP_TRY(hipGetDeviceProperties(&prop, phys_device(device)));
-        s.cus = prop.multiProcessorCount;
-    }
+    if (!s.cus)
+        if (int rc = read_cus(s, device)) return rc;
     if (!s.tables2) {
         static NttTables host[2];
         build_tables_lvl2(host);
@@ -89,7 +49,7 @@ int ensure_bk2_half_layout(DeviceState& s)
     const size_t polys = want_bk / k2N, waves = polys * k2Limbs;
     const unsigned blocks = (unsigned)((waves + kNttWavesPerBlock - 1) / kNttWavesPerBlock);
     hipLaunchKernelGGL(bk2_to_ntt_kernel, dim3(blocks), dim3(kNttThreads), kNttWavesPerBlock * kTileBytes, 0,
-                       half.p, d_bk.p, polys, s.tables2, balanced(powmod_u64(k2N, fpf::P_U64 - 2)));
+                       half.p, d_bk.p, polys, s.tables2, n_inverse(k2N));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());        // complete before any stream's kernel reads it
     s.bk2_ntt = half.release();
@@ -208,7 +168,7 @@ int cufhe_amd_lvl2_initialize(const uint64_t* bk, size_t bk_words, const uint32_
         const size_t waves = polys * k2Limbs;
         const unsigned blocks = (unsigned)((waves + kNttWavesPerBlock - 1) / kNttWavesPerBlock);
         hipLaunchKernelGGL(bk2q_to_ntt_kernel, dim3(blocks), dim3(kNttThreads), kNttWavesPerBlock * kTile512Bytes, 0,
-                           b.bk2q.p, b.d_bk.p, polys, s.tables2q, balanced(powmod_u64(k2N, fpf::P_U64 - 2)));
+                           b.bk2q.p, b.d_bk.p, polys, s.tables2q, n_inverse(k2N));
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipDeviceSynchronize());        // also: nothing on this device still reads the keys that are about to go
     }

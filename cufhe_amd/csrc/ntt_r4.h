@@ -15,7 +15,7 @@
 //
 // and over p = I^2 + 1 the product by I costs four operations (fpfield.h: mul_root4) against six: 30 operations per four
 // elements and two stages instead of 32.  The tables keep their shape; the slot of the second fine twiddle (I u, -I v) holds
-// the product u w (v w) instead (capi.hip: fill_tables with r4 = true).
+// the product u w (v w) instead (ntt_tables.h: fill_tables with r4 = true).
 //
 // What radix 4 changes is the growth of the values between reductions: the pass-through element x0 collects three
 // reduced addends per pass instead of one per stage.  The schedule is therefore no longer a chain of scalars

@@ -40,15 +40,11 @@
 #include <hip/hip_runtime.h>
 #include "fpfield.h"
 #include "ntt_r4.h"
+#include "ntt_tables.h"
 
 namespace cufhe_amd {
 
-constexpr int kN = 1024;
 constexpr int kRegs = 16;            // coefficients per lane
-constexpr int kTbCount = 15;         // per-lane twiddles of stages 4-7
-constexpr int kTcCount = 12;         // per-lane twiddles of stages 8-9
-constexpr int kTbpStride = 18;       // doubles per lambda in the packed stage 4-7 table (15 used)
-constexpr int kTcpStride = 14;       // doubles per lane in the packed stage 8-9 table (12 used)
 constexpr int kTileSlots = 66 * 16;  // 8-byte slots in a wave's transpose tile
 constexpr int kTileBytes = kTileSlots * 8;   // 8448
 
@@ -115,28 +111,7 @@ constexpr double inverse_output_bound()
 constexpr bool inverse_schedule_fits() { return inverse_output_bound() > 0 && inverse_output_bound() < 2.57; }
 static_assert(inverse_schedule_fits(), "inverse NTT lazy-reduction schedule exceeds the FP64 mantissa");
 
-// twiddle tables, generated on the host with exact integer arithmetic (capi.cpp)
-struct NttTables {
-    double tu_fwd[16];               // [k] k<15: root[2^lvl + j], lvl=floor(log2(k+1)), j=k+1-2^lvl
-    double tu_inv[16];
-    double tb_fwd[kTbCount * 16];    // [k][lambda]: root[16*2^lvl + lambda*2^lvl + j]
-    double tb_inv[kTbCount * 16];
-    double tc_fwd[kTcCount * 64];    // [k][lane]: k<4: root[256 + (lambda<<4|h<<2|k)]; else root[512 + (lambda<<5|h<<3|(k-4))]
-    double tc_inv[kTcCount * 64];
-    // The same per-lane twiddles PACKED per lane (filled for the r4 tables only): a lane's fifteen stage 4-7 twiddles and its
-    // twelve stage 8-9 twiddles are contiguous, so a transform fetches them with 8 + 6 ds_read_b128 instead of 27 ds_read_b64
-    // (the compiler pairs those into ds_read2_b64, which moves 128 B per LDS clock where ds_read_b128 moves 256).  The strides
-    // -- 18 doubles = 144 bytes per lambda, 14 doubles = 112 bytes per lane -- put the sixteen lanes of every ds_read_b128 lane
-    // group on sixteen different 4-bank slots.  [tbp_fwd | tbp_inv | tcp_fwd | tcp_inv] is one contiguous block.
-    double tbp_fwd[16 * kTbpStride];
-    double tbp_inv[16 * kTbpStride];
-    double tcp_fwd[64 * kTcpStride];
-    double tcp_inv[64 * kTcpStride];
-};
-constexpr int kLdsTablePackedDoubles = 2 * 16 * kTbpStride + 2 * 64 * kTcpStride;   // 2368
-constexpr int kLdsTablePackedBytes = kLdsTablePackedDoubles * 8;                     // 18944
-constexpr int kLdsTableDoubles = 2 * kTbCount * 16 + 2 * kTcCount * 64;   // 2016
-constexpr int kLdsTableBytes = kLdsTableDoubles * 8;                        // 16128
+// twiddle tables (NttTables): ntt_tables.h, where the host builds them with exact integer arithmetic
 
 // cooperative copy global -> LDS (whole workgroup), caller barriers afterwards
 __device__ __forceinline__ void load_tables_to_lds(double* lds, const NttTables* g)
@@ -655,7 +630,7 @@ __device__ __forceinline__ void ntt_inverse(double (&x)[kRegs], const WaveCtx& c
 
 
 // ==================================================================================================================
-// Radix-4 transforms (ntt_r4.h) on the r4 twiddle tables (capi.hip: fill_tables(..., r4 = true)) in their PACKED form
+// Radix-4 transforms (ntt_r4.h) on the r4 twiddle tables (ntt_tables.h: fill_tables(..., r4 = true)) in their PACKED form
 // (WaveCtx from make_wave_ctx_packed, LDS copy by load_packed_tables_to_lds): the same layouts,
 // layout changes and twiddle fetch placement as above, 30 instead of 32 operations per four elements and two stages,
 // and reductions only on the registers whose compile-time bound asks for one.

@@ -23,31 +23,16 @@
 //   reduce  s0 1.
 #pragma once
 #include "ntt_r4.h"
+#include "ntt_tables.h"
 #include "ntt_wave.h"
 
 namespace cufhe_amd {
 
-constexpr int kH = 512;               // points of a half transform
 constexpr int kRegs8 = 8;
 constexpr int kTile512Slots = 568;    // max slot of either map + 1
 constexpr int kTile512Bytes = kTile512Slots * 8;   // 4544
 
-// tables of ONE half transform (host: capi.hip build_tables_512)
-struct Ntt512Tables {
-    double tu_fwd[8];                 // [k] k<7: root_h[2^lvl + j], lvl = floor(log2(k+1)), j = k+1-2^lvl
-    double tu_inv[8];
-    double tb_fwd[7 * 8];             // [k][lam]: root_h[8*2^lvl + lam*2^lvl + j]
-    double tb_inv[7 * 8];
-    double tc_fwd[7 * 64];            // [k][lane]: root_h[64*2^lvl + mu*2^lvl + j], mu = 8 lam + kap
-    double tc_inv[7 * 64];
-    // radix-4 form (q4 below): the product of a block's stage-a and first stage-b twiddle, u w (forward) / v w (inverse), per lam
-    // and per lane; the wave-uniform block's sits in the spare slot 7 of tu_fwd / tu_inv.  Contiguous, in this order.
-    double uwb_fwd[8], uwb_inv[8];
-    double uwc_fwd[64], uwc_inv[64];
-};
-static_assert(sizeof(Ntt512Tables) == (16 + 1008 + 144) * 8, "Ntt512Tables: [tu 16 | tb, tc 1008 | radix-4 products 144] doubles");
-constexpr int kLds512TableDoubles = 2 * 7 * 8 + 2 * 7 * 64;     // tb_fwd .. tc_inv, contiguous: 1008
-constexpr int kLds512TableBytes = kLds512TableDoubles * 8;      // 8064 per half
+// tables of ONE half transform (Ntt512Tables): ntt_tables.h, built on the host by build_tables_512 / build_tables_lvl2q
 
 // ---- radix-4 form of the 512-point transforms (kernels_lvl2q.hip.h and the inverse waves of kernels_ll.hip.h) ----------
 // A three-stage block on the eight registers of a lane (strides 4, 2, 1; twiddles tw0 | tw1, tw2 = I tw1 | tw3..6) is one radix-4

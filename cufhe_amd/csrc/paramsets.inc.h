@@ -192,7 +192,7 @@ int ps_trgsw_to_ntt_host(int set, int device, void* stream, const uint32_t* trgs
         const size_t waves = D::bk_step_polys * PS::limbs;
         hipLaunchKernelGGL(bk_to_ntt_ps_kernel<PS>, dim3((unsigned)((waves + kNttWavesPerBlock - 1) / kNttWavesPerBlock)), dim3(kNttThreads),
                            PO::table_bytes + kNttWavesPerBlock * PO::tile_bytes, st, d_out, d_in, (size_t)D::bk_step_polys, ps_tables<PS>(s),
-                           balanced(powmod_u64(D::N, fpf::P_U64 - 2)));
+                           n_inverse(D::N));
         HIP_TRY(hipGetLastError());
         char* pin_out = (char*)blk->host + in_bytes;
         HIP_TRY(hipMemcpyAsync(pin_out, d_out, out_bytes, hipMemcpyDeviceToHost, st));
@@ -268,7 +268,7 @@ int cufhe_amd_ps_initialize(int set, const uint32_t* bk, size_t bk_words, const 
             const size_t polys = D::bk_words / D::N, waves = polys * PS::limbs;
             const unsigned blocks = (unsigned)((waves + kNttWavesPerBlock - 1) / kNttWavesPerBlock);
             hipLaunchKernelGGL(bk_to_ntt_ps_kernel<PS>, dim3(blocks), dim3(kNttThreads), PO::table_bytes + kNttWavesPerBlock * PO::tile_bytes, 0,
-                               b.bk_ntt.p, b.d_bk.p, polys, ps_tables<PS>(s), balanced(powmod_u64(D::N, fpf::P_U64 - 2)));
+                               b.bk_ntt.p, b.d_bk.p, polys, ps_tables<PS>(s), n_inverse(D::N));
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipDeviceSynchronize());        // also: nothing on this device still reads the keys that are about to go
         }
@@ -388,7 +388,7 @@ int cufhe_amd_ps_trgsw_to_ntt_batch(int set, int device, void* stream, size_t co
         const size_t polys = count * D::bk_step_polys, waves = polys * PS::limbs;
         hipLaunchKernelGGL(bk_to_ntt_ps_kernel<PS>, dim3((unsigned)((waves + kNttWavesPerBlock - 1) / kNttWavesPerBlock)), dim3(kNttThreads),
                            PO::table_bytes + kNttWavesPerBlock * PO::tile_bytes, (hipStream_t)stream, trgsw_ntt, trgsw, polys,
-                           ps_tables<PS>(g_dev[device]), balanced(powmod_u64(D::N, fpf::P_U64 - 2)));
+                           ps_tables<PS>(g_dev[device]), n_inverse(D::N));
         HIP_TRY(hipGetLastError());
         return 0;
     });

@@ -161,7 +161,8 @@ int elem(char layout, int lane, int reg)
     if (layout == 'B') return lam << 6 | reg << 2 | hi;
     return lam << 6 | hi << 4 | reg;
 }
-// r4 tables, written down from the index formulas of capi.hip (fill_tables) independently of that code
+// r4 tables, written down from the index formulas of ntt_tables.h (fill_tables) independently of that code; tests/test_ntt_tables.py
+// compares the two entry for entry (hm_r4_tables)
 double mulb(double a, double b)
 {
     const uint64_t ua = a < 0 ? P - (uint64_t)(-a) : (uint64_t)a, ub = b < 0 ? P - (uint64_t)(-b) : (uint64_t)b;
@@ -533,6 +534,26 @@ int hm_check_mulmod_add(const double* a, const double* w, const double* c, int c
         if (std::fabs(r) > bound * fpf::P || r != std::nearbyint(r)) bad++;
     }
     return bad;
+}
+
+// The r4 tables of the transcription in r4m, for the comparison with the library's builder:
+// out = [tu_fwd 15 | tu_inv 15 | tb_fwd 15 x 16 ([k][lam]) | tb_inv | tc_fwd 12 x 64 ([k][lane]) | tc_inv]
+void hm_r4_tables(double* out)
+{
+    tables();
+    for (int dir = 0; dir < 2; dir++) {
+        const std::vector<double>& root = dir ? g_inv : g_fwd;
+        const r4m::Block u = r4m::block_r4(root, 1, 0);
+        for (int k = 0; k < 15; k++) out[dir * 15 + k] = u(k);
+        for (int lam = 0; lam < 16; lam++) {
+            const r4m::Block b = r4m::block_r4(root, 16, lam);
+            for (int k = 0; k < 15; k++) out[30 + dir * 240 + k * 16 + lam] = b(k);
+        }
+        for (int lane = 0; lane < 64; lane++) {
+            const r4m::BlockC c = r4m::block_c_r4(root, lane);
+            for (int k = 0; k < 12; k++) out[510 + dir * 768 + k * 64 + lane] = c(k);
+        }
+    }
 }
 
 double hm_p(void) { return fpf::P; }
