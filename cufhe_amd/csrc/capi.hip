@@ -836,7 +836,7 @@ int lower_gates(const P& p, hipStream_t st, int level, size_t count, GetGate get
 }
 
 // The TRLWE-level operations recorded through the scheduler (include/cufhe_gpu.cuh:124-146,209-216,282-285;
-// src/cufhe_gates_gpu.cu:86-146) on BasePath or a PsPath<PS>: any mix of
+// src/cufhe_gates_gpu.cu:86-146) or given as a batch (trlwe_batch below) on BasePath or a PsPath<PS>: any mix of
 //   CUFHE_AMD_TL_BOOTSTRAP  lvl0 TLWE -> TRLWE     __BlindRotateGlobal__, src/bootstrap_gpu.cu:317-323
 //   CUFHE_AMD_TL_REFRESH    TRLWE -> TRLWE         __SEIandBootstrap2TRLWE__, :325-364
 //   CUFHE_AMD_TL_SEIKS      TRLWE -> lvl0 TLWE     __SEIandKS__, src/keyswitch_gpu.cu:26-40
@@ -885,7 +885,8 @@ int lower_trlwe_ops(const P& p, hipStream_t st, const GateRef* g, size_t n)
         if (n_cb == n) return 0;
     }
     Scratch sc;
-    const size_t need = (n_se * P::mid_words + n_t0 * P::lvl0_words + n_rot * tw) * 4 + (3 * n + 8) * sizeof(LinDesc) +
+    // descriptors: a Refresh has one in each of four lists (se, ks, rot, scat), every other operation fewer
+    const size_t need = (n_se * P::mid_words + n_t0 * P::lvl0_words + n_rot * tw) * 4 + (4 * n + 8) * sizeof(LinDesc) +
                         n_cmux * sizeof(CmuxDesc) + n_cmuxr * sizeof(CmuxRotDesc) + 16384;
     if (int rc = open_scratch(s, st, need, &sc)) return rc;
     if (n_cmux) {      // the CMUXNTT calls of this level: independent of its other operations (the scheduler's contract); needs no key
@@ -978,20 +979,17 @@ struct BasePath {
     int ready() const { return s.keys_ready ? 0 : fail(-3, "Initialize(ek) has not been called for this device"); }
     int rotate(hipStream_t st, const LinDesc* d, size_t count, int steps, uint32_t* dump) const { return launch_blind_rotate(s, st, d, count, steps, dump); }
     int keyswitch(hipStream_t st, const LinDesc* d, size_t count) const { return launch_keyswitch(s, st, d, count); }
-    int cmux(hipStream_t st, const CmuxDesc* d, size_t count) const
+    // one wave per descriptor, kNttWavesPerBlock of them beside the workgroup's copy of the tables: both CMUX kernels
+    template <class Desc>
+    int launch_cmux(void (*kernel)(const Desc*, int, const NttTables*), hipStream_t st, const Desc* d, size_t count) const
     {
         const unsigned blocks = (unsigned)((count + kNttWavesPerBlock - 1) / kNttWavesPerBlock);
-        hipLaunchKernelGGL(cmux_desc_kernel, dim3(blocks), dim3(kNttThreads), kNttLdsBytes, st, d, (int)count, s.tables);
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kNttThreads), kNttLdsBytes, st, d, (int)count, s.tables);
         HIP_TRY(hipGetLastError());
         return 0;
     }
-    int cmux_rotate(hipStream_t st, const CmuxRotDesc* d, size_t count) const
-    {
-        const unsigned blocks = (unsigned)((count + kNttWavesPerBlock - 1) / kNttWavesPerBlock);
-        hipLaunchKernelGGL(cmux_rotate_desc_kernel, dim3(blocks), dim3(kNttThreads), kNttLdsBytes, st, d, (int)count, s.tables);
-        HIP_TRY(hipGetLastError());
-        return 0;
-    }
+    int cmux(hipStream_t st, const CmuxDesc* d, size_t count) const { return launch_cmux(cmux_desc_kernel, st, d, count); }
+    int cmux_rotate(hipStream_t st, const CmuxRotDesc* d, size_t count) const { return launch_cmux(cmux_rotate_desc_kernel, st, d, count); }
 };
 
 template <class GetGate>
@@ -1031,6 +1029,16 @@ int direct_batch(DeviceState& s, hipStream_t st, size_t count, Make make, Launch
     Desc* d;
     if (int rc = upload_descs(s, sc, h, &d)) return rc;
     return launch(d);
+}
+
+// The TRLWE-level batch entry points (cufhe_amd_refresh_batch / sample_extract*_keyswitch_batch / cmux*_batch, cufhe_amd_ps_cmux_batch):
+// item g is the TRLWE-level operation make(g), the batch one level of lower_trlwe_ops on `path` -- what the scheduler launches for it
+template <class P, class Make>
+int trlwe_batch(const P& path, hipStream_t st, size_t count, Make make)
+{
+    std::vector<GateRef> refs(count);
+    for (size_t g = 0; g < count; g++) refs[g] = make(g);
+    return lower_trlwe_ops(path, st, refs.data(), count);
 }
 
 // A device allocation of an Initialize call (through init_malloc, on the current device): freed on that device when the owner goes
@@ -1572,11 +1580,9 @@ int cufhe_amd_cmux_batch(int device, void* stream, size_t count, const double* t
     }
     if (!trgsw_ntt || !c1 || !c0 || !res) return fail(-1, "null pointer");
     if (count == 0) return 0;
-    const unsigned blocks = (unsigned)((count + kNttWavesPerBlock - 1) / kNttWavesPerBlock);
-    hipLaunchKernelGGL(cmux_kernel, dim3(blocks), dim3(kNttThreads), kNttLdsBytes, (hipStream_t)stream, res, trgsw_ntt,
-                       c1, c0, (int)count, g_dev[device].tables);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return trlwe_batch(BasePath{g_dev[device]}, (hipStream_t)stream, count, [&](size_t g) {
+        return GateRef{CUFHE_AMD_TL_CMUX, res + g * 2 * kN, c1 + g * 2 * kN, c0 + g * 2 * kN, (const uint32_t*)(trgsw_ntt + g * kBkStepDoubles)};
+    });
 }
 
 int cufhe_amd_sample_extract_keyswitch_batch(int device, void* stream, size_t count, const uint32_t* trlwe, uint32_t* tlwe0)
@@ -1586,19 +1592,9 @@ int cufhe_amd_sample_extract_keyswitch_batch(int device, void* stream, size_t co
     if (!s.keys_ready) return fail(-3, "Initialize(ek) has not been called for this device");
     if (!trlwe || !tlwe0) return fail(-1, "null pointer");
     if (count == 0) return 0;
-    hipStream_t st = (hipStream_t)stream;
-    Scratch sc;
-    if (int rc = open_scratch(s, st, count * (kLvl1Words * sizeof(uint32_t) + sizeof(LinDesc)) + 8192, &sc)) return rc;
-    uint32_t* t1;
-    if (int rc = sc.alloc((void**)&t1, count * kLvl1Words * sizeof(uint32_t))) return rc;
-    hipLaunchKernelGGL(sample_extract_kernel, dim3((unsigned)(count < 2048 ? count : 2048)), dim3(256), 0, st, t1, trlwe, (int)count);
-    HIP_TRY(hipGetLastError());
-    std::vector<LinDesc> ks(count);
-    for (size_t g = 0; g < count; g++)
-        ks[g] = {t1 + g * kLvl1Words, t1 + g * kLvl1Words, tlwe0 + g * kLvl0Words, 1, 0, 0u, 0u};
-    LinDesc* d;
-    if (int rc = upload_descs(s, sc, ks, &d)) return rc;
-    return launch_keyswitch(s, st, d, count);
+    return trlwe_batch(BasePath{s}, (hipStream_t)stream, count, [&](size_t g) {
+        return GateRef{CUFHE_AMD_TL_SEIKS, tlwe0 + g * kLvl0Words, trlwe + g * 2 * kN, nullptr, nullptr};
+    });
 }
 
 // ---- packed ROM words ----
@@ -1642,34 +1638,12 @@ int cufhe_amd_cmux_rotate_batch(int device, void* stream, size_t count, const do
         std::lock_guard<std::mutex> lk(g_mu);
         if (int rc = ensure_ntt(device)) return rc;
     }
-    DeviceState& s = g_dev[device];
-    hipStream_t st = (hipStream_t)stream;
-    Scratch sc;
-    if (int rc = open_scratch(s, st, count * sizeof(int32_t) + 4096, &sc)) return rc;
-    int32_t* dexps;
-    if (int rc = upload_descs(s, sc, std::vector<int32_t>(exps, exps + count), &dexps)) return rc;
-    const unsigned blocks = (unsigned)((count + kNttWavesPerBlock - 1) / kNttWavesPerBlock);
-    hipLaunchKernelGGL(cmux_rotate_kernel, dim3(blocks), dim3(kNttThreads), kNttLdsBytes, st, res, trgsw_ntt, c, dexps, (int)count, s.tables);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    // one selector for the launch: every item names the same TRGSW
+    return trlwe_batch(BasePath{g_dev[device]}, (hipStream_t)stream, count, [&](size_t g) {
+        return GateRef{CUFHE_AMD_TL_CMUX_ROTATE(exps[g]), res + g * 2 * kN, c + g * 2 * kN, nullptr, (const uint32_t*)trgsw_ntt};
+    });
 }
 
-// the indexed extraction of both entries below into tlwe1 (device, [count][N+1]); sc: the open scratch of the call
-static int launch_sample_extract_index(DeviceState& s, Scratch& sc, size_t count, const uint32_t* trlwe, const int32_t* src,
-                                       const int32_t* idx, uint32_t* tlwe1)
-{
-    std::vector<int32_t> h(2 * count);      // [src | idx], one staged copy
-    for (size_t g = 0; g < count; g++) {
-        h[g] = src ? src[g] : (int32_t)g;
-        h[count + g] = idx[g];
-    }
-    int32_t* d;
-    if (int rc = upload_descs(s, sc, h, &d)) return rc;
-    hipLaunchKernelGGL(sample_extract_index_kernel, dim3((unsigned)(count < 2048 ? count : 2048)), dim3(256), 0, sc.st, tlwe1, trlwe, d,
-                       d + count, (int)count);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
 static int check_extract_index_args(size_t count, const uint32_t* trlwe, const int32_t* src, const int32_t* idx, const uint32_t* out)
 {
     if (!trlwe || !idx || !out) return fail(-1, "null pointer");
@@ -1689,10 +1663,15 @@ int cufhe_amd_sample_extract_index_batch(int device, void* stream, size_t count,
     if (int rc = check_extract_index_args(count, trlwe, src, idx, tlwe1)) return rc;
     if (count == 0) return 0;
     if (int rc = use_device(device)) return rc;
-    DeviceState& s = g_dev[device];
-    Scratch sc;
-    if (int rc = open_scratch(s, (hipStream_t)stream, 2 * count * sizeof(int32_t) + 4096, &sc)) return rc;
-    return launch_sample_extract_index(s, sc, count, trlwe, src, idx, tlwe1);
+    hipStream_t st = (hipStream_t)stream;
+    return direct_batch(g_dev[device], st, count, [&](size_t g) {
+        const uint32_t* in = trlwe + (size_t)(src ? src[g] : g) * 2 * kN;
+        return LinDesc{in, in, tlwe1 + g * kLvl1Words, 1, 0, 0u, (uint32_t)idx[g]};
+    }, [&](const LinDesc* d) {
+        hipLaunchKernelGGL(sample_extract_index_desc_kernel, dim3((unsigned)(count < 2048 ? count : 2048)), dim3(256), 0, st, d, (int)count);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    });
 }
 
 int cufhe_amd_sample_extract_index_keyswitch_batch(int device, void* stream, size_t count, const uint32_t* trlwe, const int32_t* src,
@@ -1705,18 +1684,9 @@ int cufhe_amd_sample_extract_index_keyswitch_batch(int device, void* stream, siz
     if (int rc = check_extract_index_args(count, trlwe, src, idx, tlwe0)) return rc;
     if (count == 0) return 0;
     if (int rc = use_device(device)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    Scratch sc;
-    if (int rc = open_scratch(s, st, count * (kLvl1Words * sizeof(uint32_t) + sizeof(LinDesc) + 2 * sizeof(int32_t)) + 8192, &sc)) return rc;
-    uint32_t* t1;
-    if (int rc = sc.alloc((void**)&t1, count * kLvl1Words * sizeof(uint32_t))) return rc;
-    if (int rc = launch_sample_extract_index(s, sc, count, trlwe, src, idx, t1)) return rc;
-    std::vector<LinDesc> ks(count);
-    for (size_t g = 0; g < count; g++)
-        ks[g] = {t1 + g * kLvl1Words, t1 + g * kLvl1Words, tlwe0 + g * kLvl0Words, 1, 0, 0u, 0u};
-    LinDesc* d;
-    if (int rc = upload_descs(s, sc, ks, &d)) return rc;
-    return launch_keyswitch(s, st, d, count);
+    return trlwe_batch(BasePath{s}, (hipStream_t)stream, count, [&](size_t g) {
+        return GateRef{CUFHE_AMD_TL_SEIKS_AT(idx[g]), tlwe0 + g * kLvl0Words, trlwe + (size_t)(src ? src[g] : g) * 2 * kN, nullptr, nullptr};
+    });
 }
 
 int cufhe_amd_refresh_batch(int device, void* stream, size_t count, const uint32_t* trlwe_in, uint32_t* trlwe_out)
@@ -1726,24 +1696,9 @@ int cufhe_amd_refresh_batch(int device, void* stream, size_t count, const uint32
     if (!s.keys_ready) return fail(-3, "Initialize(ek) has not been called for this device");
     if (!trlwe_in || !trlwe_out) return fail(-1, "null pointer");
     if (count == 0) return 0;
-    hipStream_t st = (hipStream_t)stream;
-    Scratch sc;
-    if (int rc = open_scratch(s, st, count * ((kLvl1Words + kLvl0Words) * sizeof(uint32_t) + 2 * sizeof(LinDesc)) + 16384, &sc)) return rc;
-    uint32_t *t1, *t0;
-    if (int rc = sc.alloc((void**)&t1, count * kLvl1Words * sizeof(uint32_t))) return rc;
-    if (int rc = sc.alloc((void**)&t0, count * kLvl0Words * sizeof(uint32_t))) return rc;
-    hipLaunchKernelGGL(sample_extract_kernel, dim3((unsigned)(count < 2048 ? count : 2048)), dim3(256), 0, st, t1, trlwe_in, (int)count);
-    HIP_TRY(hipGetLastError());
-    std::vector<LinDesc> ks(count), rot(count);
-    for (size_t g = 0; g < count; g++) {
-        ks[g] = {t1 + g * kLvl1Words, t1 + g * kLvl1Words, t0 + g * kLvl0Words, 1, 0, 0u, 0u};
-        rot[g] = {t0 + g * kLvl0Words, t0 + g * kLvl0Words, nullptr, 1, 0, 0u, 0u};
-    }
-    LinDesc *dks, *drot;
-    if (int rc = upload_descs(s, sc, ks, &dks)) return rc;
-    if (int rc = upload_descs(s, sc, rot, &drot)) return rc;
-    if (int rc = launch_keyswitch(s, st, dks, count)) return rc;
-    return launch_blind_rotate(s, st, drot, count, kLvl0N, trlwe_out);
+    return trlwe_batch(BasePath{s}, (hipStream_t)stream, count, [&](size_t g) {
+        return GateRef{CUFHE_AMD_TL_REFRESH, trlwe_out + g * 2 * kN, trlwe_in + g * 2 * kN, nullptr, nullptr};
+    });
 }
 
 int cufhe_amd_polymul_batch(int device, void* stream, size_t count, const int32_t* a, const uint32_t* b, uint32_t* res)

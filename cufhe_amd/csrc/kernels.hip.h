@@ -11,9 +11,9 @@
 //   keyswitch_direct_kernel                        the key switch with one / eight workgroups per ciphertext, rows straight from L2
 //                                                  (small launches: lowest latency; the low-latency blind rotations are in
 //                                                  kernels_ll.hip.h)
-//   sample_extract_kernel, cmux_kernel             SEIandKS / Refresh / CMUXNTT pieces
+//   sample_extract_desc_kernel, cmux_desc_kernel   SEIandKS / Refresh / CMUXNTT pieces
 //                                                   src/keyswitch_gpu.cu:26-40, src/bootstrap_gpu.cu:197-285
-//   sample_extract_index_kernel, trlwe_rotate_kernel, cmux_rotate_kernel
+//   sample_extract_index_desc_kernel, trlwe_rotate_kernel, cmux_rotate_desc_kernel
 //                                                  packed ROM words: __SampleExtractIndex__ at a run-time index
 //                                                  (src/bootstrap_gpu.cu:366-381), X^e on a TRLWE, the CMUX of c and X^e c
 //   polymul_kernel         the NTT product check of test/test_polynomial_mult_1024.cu:76-99
@@ -810,19 +810,7 @@ __global__ __launch_bounds__(kKsThreads) void keyswitch_direct_kernel(
     }
 }
 
-// __SampleExtractIndex__<P,0> on TRLWEs in global memory: trlwe[count][2N] -> tlwe1[count][N+1]
-__global__ __launch_bounds__(256) void sample_extract_kernel(uint32_t* __restrict__ tlwe1,
-                                                             const uint32_t* __restrict__ trlwe, int count)
-{
-    for (int g = blockIdx.x; g < count; g += gridDim.x) {
-        const uint32_t* in = trlwe + (size_t)g * 2 * kN;
-        uint32_t* o = tlwe1 + (size_t)g * kLvl1Words;
-        for (int m = threadIdx.x; m <= kN; m += blockDim.x)
-            o[m] = (m == kN) ? in[kN] : (m == 0 ? in[0] : 0u - in[kN - m]);
-    }
-}
-
-// the same with one descriptor per TRLWE: in0 = trlwe (2N words), out = lvl1 TLWE (N + 1 words)
+// __SampleExtractIndex__<P,0> on TRLWEs in global memory, one descriptor per TRLWE: in0 = trlwe (2N words), out = lvl1 TLWE (N + 1 words)
 __global__ __launch_bounds__(256) void sample_extract_desc_kernel(const LinDesc* __restrict__ descs, int count)
 {
     for (int g = blockIdx.x; g < count; g += gridDim.x) {
@@ -843,14 +831,7 @@ __device__ __forceinline__ void sample_extract_index_block(uint32_t* __restrict_
     for (int m = threadIdx.x; m <= kN; m += blockDim.x)
         o[m] = (m == kN) ? in[kN + j] : (m <= j ? in[j - m] : 0u - in[kN + j - m]);
 }
-// tlwe1[g] = SampleExtract(idx[g])(trlwe[src[g]]): several outputs may name one source; src[g] is the caller's contract (no length here)
-__global__ __launch_bounds__(256) void sample_extract_index_kernel(uint32_t* __restrict__ tlwe1, const uint32_t* __restrict__ trlwe,
-                                                                   const int32_t* __restrict__ src, const int32_t* __restrict__ idx, int count)
-{
-    for (int g = blockIdx.x; g < count; g += gridDim.x)
-        sample_extract_index_block(tlwe1 + (size_t)g * kLvl1Words, trlwe + (size_t)src[g] * 2 * kN, idx[g] & (kN - 1));
-}
-// the same with one descriptor per output: in0 = trlwe (2N words), out = lvl1 TLWE (N + 1 words), pad = the index
+// one descriptor per output: in0 = trlwe (2N words), out = lvl1 TLWE (N + 1 words), pad = the index; several outputs may name one source
 __global__ __launch_bounds__(256) void sample_extract_index_desc_kernel(const LinDesc* __restrict__ descs, int count)
 {
     for (int g = blockIdx.x; g < count; g += gridDim.x)
@@ -959,22 +940,7 @@ __device__ __forceinline__ void cmux_wave(uint32_t* o, const double2* key, const
     }
 }
 
-__global__ __launch_bounds__(kNttThreads) void cmux_kernel(
-    uint32_t* res, const double* __restrict__ trgsw_ntt, const uint32_t* c1, const uint32_t* c0, int count,
-    const NttTables* __restrict__ gt)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    load_tables_to_lds((double*)smem, gt);
-    __syncthreads();
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int g = blockIdx.x * kNttWavesPerBlock + wave;
-    if (g >= count) return;
-    const WaveCtx ctx = make_wave_ctx(smem, kLdsTableBytes + wave * kTileBytes, 0, gt, lane);
-    cmux_wave(res + (size_t)g * 2 * kN, (const double2*)(trgsw_ntt + (size_t)g * kBkStepDoubles), c1 + (size_t)g * 2 * kN,
-              c0 + (size_t)g * 2 * kN, ctx, lane);
-}
-
-// the same on per-operation pointers: what the stream scheduler launches for the CMUXNTT calls of one dependence level
+// CMUXNTT on per-operation pointers: the CMUXNTT calls of one dependence level of the stream scheduler, or the items of cufhe_amd_cmux_batch
 struct CmuxDesc {
     const uint32_t* c1;
     const uint32_t* c0;
@@ -994,24 +960,9 @@ __global__ __launch_bounds__(kNttThreads) void cmux_desc_kernel(const CmuxDesc* 
     cmux_wave(d.res, (const double2*)d.trgsw_ntt, d.c1, d.c0, ctx, lane);
 }
 
-// The rotating CMUX of a batch: res[g] = c[g] + trgsw [x] (X^(exps[g]) c[g] - c[g]) with ONE selector for the launch (an address bit
-// of a packed ROM acts on every TRLWE of the table); res may be c
-__global__ __launch_bounds__(kNttThreads) void cmux_rotate_kernel(
-    uint32_t* res, const double* __restrict__ trgsw_ntt, const uint32_t* c, const int32_t* __restrict__ exps, int count,
-    const NttTables* __restrict__ gt)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    load_tables_to_lds((double*)smem, gt);
-    __syncthreads();
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int g = blockIdx.x * kNttWavesPerBlock + wave;
-    if (g >= count) return;
-    const WaveCtx ctx = make_wave_ctx(smem, kLdsTableBytes + wave * kTileBytes, 0, gt, lane);
-    const uint32_t e = __builtin_amdgcn_readfirstlane((uint32_t)exps[g]);
-    cmux_wave<true>(res + (size_t)g * 2 * kN, (const double2*)trgsw_ntt, nullptr, c + (size_t)g * 2 * kN, ctx, lane, e);
-}
-
-// ... and on per-operation pointers, beside cmux_desc_kernel: the scheduler's cufhe_amd_enqueue_cmux_rotate calls of one dependence level
+// The rotating CMUX res = c + trgsw [x] (X^e c - c) on per-operation pointers, beside cmux_desc_kernel; res may be c.  The scheduler's
+// cufhe_amd_enqueue_cmux_rotate calls of one dependence level, or the items of cufhe_amd_cmux_rotate_batch: there every descriptor names
+// the ONE selector of the launch (an address bit of a packed ROM acts on every TRLWE of the table)
 struct CmuxRotDesc {
     const uint32_t* c;
     uint32_t* res;

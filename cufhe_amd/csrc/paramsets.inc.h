@@ -410,16 +410,10 @@ int cufhe_amd_ps_cmux_batch(int set, int device, void* stream, size_t count, con
         if constexpr (PS::small_modulus) {
             return fail(-1, "CMUXNTT: the small-modulus build of the reference has none (src/cufhe_gates_gpu.cu:68-86)");
         } else {
-            DeviceState& s = g_dev[device];
-            hipStream_t st = (hipStream_t)stream;
             constexpr size_t tw = (size_t)D::K1 * D::N;
-            std::vector<CmuxDesc> cm(count);
-            for (size_t g = 0; g < count; g++) cm[g] = {c1 + g * tw, c0 + g * tw, res + g * tw, trgsw_ntt + g * D::bk_ntt_step_doubles};
-            Scratch sc;
-            if (int rc = open_scratch(s, st, count * sizeof(CmuxDesc) + 4096, &sc)) return rc;
-            CmuxDesc* d;
-            if (int rc = upload_descs(s, sc, cm, &d)) return rc;
-            return ps_launch_cmux<PS>(s, st, d, count);
+            return trlwe_batch(PsPath<PS>{g_dev[device], ps_state(set, device)}, (hipStream_t)stream, count, [&](size_t g) {
+                return GateRef{CUFHE_AMD_TL_CMUX, res + g * tw, c1 + g * tw, c0 + g * tw, (const uint32_t*)(trgsw_ntt + g * D::bk_ntt_step_doubles)};
+            });
         }
     });
 }

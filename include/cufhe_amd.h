@@ -287,7 +287,7 @@ int cufhe_amd_keyswitch_batch(int device, void* stream, size_t count, const uint
 int cufhe_amd_sample_extract_keyswitch_batch(int device, void* stream, size_t count,
                                              const uint32_t* trlwe, uint32_t* tlwe0);
 /* Refresh (src/cufhe_gates_gpu.cu:106-124, SEIandBootstrap2TRLWE src/bootstrap_gpu.cu:325-364):
- * trlwe_in[count][2N] -> sample extract -> key switch -> blind rotate -> trlwe_out[count][2N] */
+ * trlwe_in[count][2N] -> sample extract -> key switch -> blind rotate -> trlwe_out[count][2N]; trlwe_out may be trlwe_in */
 int cufhe_amd_refresh_batch(int device, void* stream, size_t count, const uint32_t* trlwe_in,
                             uint32_t* trlwe_out);
 /* TRGSW2NTT (src/bootstrap_gpu.cu:75-94): trgsw[count][(k+1)l][k+1][N] torus words ->

@@ -563,6 +563,30 @@ def test_trlwe_level_primitives(engine, keys, oracle):
         assert np.array_equal(got[g], want)
 
 
+def test_refresh_batch_in_place(engine, keys, oracle):
+    """refresh_batch with trlwe_out == trlwe_in at 9 TRLWEs (one 8-rotation workgroup plus one): the rotations' results go through
+    scratch and are copied over their own inputs, so every row must still be the oracle's sample extract -> key switch ->
+    blind rotate of the row that was there before the call."""
+    count = 9
+    bits = np.array([1, 0, 0, 1, 1, 0, 1, 1, 0], np.uint8)
+    cts = keys.encrypt(bits, 0, seed=334)
+    trl = np.zeros((count, 2 * ol.N), np.uint32)
+    for g in range(count):
+        oracle.orc_blind_rotate(keys.ek, trl[g], np.ascontiguousarray(cts[g]), -1)
+    dtrl = _upload(engine, trl)
+    engine.api.refresh_batch(dtrl, dtrl, count)
+    got = dtrl.download().reshape(count, -1)
+    for g in range(count):
+        t0 = np.zeros(ol.n + 1, np.uint32)
+        oracle.orc_sample_extract_keyswitch(keys.ek, t0, np.ascontiguousarray(trl[g]))
+        want = np.zeros(2 * ol.N, np.uint32)
+        oracle.orc_blind_rotate(keys.ek, want, t0, -1)
+        assert np.array_equal(got[g], want), g
+        t1 = np.zeros(ol.N + 1, np.uint32)
+        oracle.orc_sample_extract0(t1, np.ascontiguousarray(got[g]))
+        assert keys.decrypt(t1, 1)[0] == bits[g]
+
+
 @pytest.mark.parametrize("count", [1, 7, 9, 17, 129, 300, 1031])
 def test_ragged_batch_sizes(engine, keys, count):
     """Batch sizes that are not multiples of the 8-rotation / 16-ciphertext workgroups, on both
