@@ -21,6 +21,7 @@
 
 #include "../../include/cufhe_amd.h"
 #include "sched_core.h"
+#include "launch_plan.h"
 #include "kernels.hip.h"
 #include "kernels_lvl2.hip.h"
 #include "kernels_lvl2q.hip.h"
@@ -106,60 +107,11 @@ int phys_device(int device)
     if (g_share_devices && g_phys_count > 0) return (g_device_base + device) % g_phys_count;
     return device + g_device_base;
 }
-long g_ks_split_threshold = -1; // key switches per launch up to which each ciphertext is split over 8 workgroups
-// Key switch launch shape, -1 = the measured rule (tools/ks_slices.py, MI355X, ms per launch of n key switches):
-//   8 workgroups per ciphertext   0.046 (n = 1)  0.049 (16)  0.051 (32)  0.078 (64)  0.13 (128)  0.24 (256)  0.45 (512)  0.85 (1024)
-//   a workgroup per ciphertext    0.22 (n <= 256)  0.42 (512)  0.80 (1024)  1.19 (1536)  1.63 (2048)  3.3 (4096)
-//   table through LDS (keyswitch_kernel), 16 ciphertexts per workgroup and the steps of j cut into runs that fill the CUs:
-//                                 0.040 (1)  0.052 (16)  0.059 (32)  0.070 (64)  0.084 (128)  0.12 (256)  0.19 (512)  0.32 (1024)
-//                                 0.56 (1536)  0.58 (2048)  0.86 (3072)  1.04 - 1.09 (4096)
-// so: split up to 32, the shared-table kernel above -- on 256 CUs; in units of the device's CU count: 1/8 ciphertext per CU.
-// The workgroup-per-ciphertext kernel is no longer chosen by the rule ("ks_wg_threshold" still forces it).
-inline long ks_auto_split(int cus) { return std::max(1, cus) / 8; }
-inline long ks_auto_wg(int) { return 0; }
-long g_ll2_threshold = -1;      // two-rotations-per-workgroup low-latency kernel: -1 by cost, 0 never, > 0 for launches up to this size
-long g_ks_wg_threshold = -1;    // key switches per launch up to which the workgroup-per-ciphertext kernel is used
-long g_ks_per_wg = -1;          // ciphertexts per workgroup of the shared-table key switch: -1 by count, else 1..16
-long g_ks_slices = -1;          // runs the shared-table key switch cuts j into: -1 by count, else a power of two 1..64
-// The shape of a shared-table launch (keyswitch_kernel: per_wg ciphertexts per workgroup, the kn steps of j cut into `slices` runs):
-// the cheapest by a model of the measured times -- a workgroup of 16 live waves takes 1.03 us per step (0.68 + 0.022 per live wave),
-// 12 us around its steps; the workgroups run in rounds of one per CU (hipDeviceProp_t::multiProcessorCount, cached in
-// DeviceState); a launch with runs zeroes the outputs first.  kn = 1024 -- 4096 ciphertexts: 256 workgroups x 1024 steps; 3072:
-// 768 x 256 (three rounds); 2048: 256 x 512; 256: 256 x 64.  min_slices: a workgroup keeps the digit words of at most 1024 steps.
-void ks_auto_shape(size_t count, int cus, int kn, int min_slices, int* per_wg, int* slices)
-{
-    const size_t c = cus > 0 ? (size_t)cus : 256;
-    if (g_ks_slices > 0 || g_ks_per_wg > 0) {            // forced (tests, sweeps): the other one by the round-5 rule
-        const size_t p = (count + c - 1) / c;
-        *per_wg = g_ks_per_wg > 0 ? (int)g_ks_per_wg : (int)(p < 1 ? 1 : p > 16 ? 16 : p);
-        *slices = std::max(min_slices, g_ks_slices > 0 ? (int)g_ks_slices : 1);
-        return;
-    }
-    auto cost = [&](int p, int sl) {                      // us
-        const size_t wgs = (count + p - 1) / p * sl, rounds = (wgs + c - 1) / c;
-        return rounds * (kn / sl * (0.68 + 0.022 * p) + 12.0) + (sl > 1 ? 20.0 : 15.0);
-    };
-    const size_t fit = (count * min_slices + c - 1) / c;  // fewest ciphertexts per workgroup that still fit one round
-    int best_p = (int)(fit < 1 ? 1 : fit > 16 ? 16 : fit), best_sl = min_slices;
-    double best = cost(best_p, best_sl);
-    for (int sl = min_slices; sl <= 64; sl *= 2) {
-        const double t = cost(kKsWaves, sl);
-        if (t < best) { best = t; best_p = kKsWaves; best_sl = sl; }
-    }
-    *per_wg = best_p;
-    *slices = best_sl;
-}
-long g_ll_threshold = -1;      // rotations per launch up to which the 16-wave split-transform kernel is used; -1: by measured cost (below)
-long g_half_threshold = -1;    // ... up to which the batch kernel runs one rotation per SIMD (4 per workgroup); -1: by measured cost
-// "br_shape": 0 = by the rules of launch_blind_rotate; 1 / 2 / 3 = every launch whole on the batch kernel (8 rotations per workgroup) / the
+// the launch-shape options ("ll_threshold", "ks_slices", ...: launch_plan.h); cus_of(s) and this are what every plan is made from
+plan::Tuning g_tuning;
+// "br_shape": 0 = by the rules of plan::plan_blind_rotate; 1 / 2 / 3 = every launch whole on the batch kernel (8 rotations per workgroup) / the
 // paired low-latency kernel (2 per workgroup) / the single one.  thread_local: the scheduler's launch worker picks a shape per launch.
 thread_local long g_br_shape = 0;
-long g_tail_split = 1;         // 1: launches above one grid round are cut into full rounds + a tail that takes the cheapest kernel
-// N = 2048 blind rotation: 1 = four quarter waves per rotation, two rotations per CU (kernels_lvl2q.hip.h); 0 = eight half waves, one
-// rotation per CU (kernels_lvl2.hip.h); -1 = by measured cost: a launch that leaves CUs with a single rotation (<= one per CU) is
-// faster on the eight-wave kernel (256 rotations: 14.5 ms against 17.4), everything above on the four-wave one (512: 27.3 against 28.0,
-// 4096: 192 against 223)
-long g_lvl2_kernel = -1;
 long g_lvl0_ring = 1024;       // ring through which gates on lvl0 ciphertexts bootstrap: 1024 (lvl01/lvl10) or 2048 (lvl02/lvl20)
 constexpr int kMaxLogicalDevices = 64;    // SetGPUNum bound (per-device tables of fixed size: paramsets.inc.h)
 std::deque<DeviceState> g_dev(1);    // re-created only while no device is initialised (SetGPUNum)
@@ -420,97 +372,46 @@ int launch_blind_rotate(DeviceState& s, hipStream_t st, const LinDesc* d, size_t
         HIP_TRY(hipFuncSetAttribute((const void*)blind_rotate_ll2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kLl2LdsBytes));
         s.br_lds_opt_in = true;
     }
-    // One round of the batch kernel's grid is a workgroup of 8 rotations per CU and takes ~19 ms however few of its
-    // wave slots are used, so a launch of a few rotations past a whole round used to cost two rounds.  Launches are cut into
-    // whole rounds plus a tail, and the tail takes the cheapest of: the low-latency kernel (a CU per
-    // rotation, 3.3 ms per started round of one rotation per CU), its paired form (two per CU, 5.3 - 5.8 ms), the batch
-    // kernel with one rotation per SIMD (~12 ms per round of four per CU), a full round.  All variants compute identical
-    // words.  Every rule below is in units of the device's CU count (MI355X: 256; the measured milliseconds are that chip's).
-    const size_t cu = (size_t)std::max(1, cus_of(s));
-    const size_t kRound = cu * kBrWavesPerBlock;
-    auto launch_batch = [&](const LinDesc* dd, size_t n, int active, uint32_t* dump) {
-        const unsigned blocks = (unsigned)((n + active - 1) / active);
-        hipLaunchKernelGGL(blind_rotate_kernel, dim3(blocks), dim3(kBrThreads), kBrLdsBytes, st, dd, (int)n,
-                           s.bk_ntt, s.tables_r4, steps, dump, active, s.tvs);
-    };
-    // Measured on MI355X, 256 CUs (tools/latency_sweep.py, tools/ll_times.py; profiles/r02_latency_sweep.txt, r05_ll_ab.txt), ms per
-    // launch of n rotations, key switch included:
-    //   low-latency kernel  2.9 (n <= 64), 3.3 / 6.7 / 10.0 / 13.3 / 16.6 per started round of one rotation per CU
-    //   its paired form     5.0 - 5.3 per started round of two per CU (10.4 for four, 17.1 for six, 22.9 for eight)
-    //   one rotation per SIMD 12.7 (n <= 4 per CU)          two per SIMD 20.7 (n <= 8 per CU)
-    // so: low-latency up to one rotation per CU, rounds of two per CU on the paired kernel (+ a last round of up to one per CU on
-    // the single one) up to six per CU, a full round of the batch kernel above.  ("ll2_threshold" 0 gives the rules without the
-    // paired kernel: low-latency up to three per CU, one-per-SIMD up to four, both up to five.)
-    const bool auto_ll = g_ll_threshold < 0, auto_half = g_half_threshold < 0;
-    auto launch_ll = [&](const LinDesc* dd, size_t n, uint32_t* dump) {
-        // smallest batches: one 16-wave workgroup per rotation, transforms split in halves (kernels_ll.hip.h)
-        hipLaunchKernelGGL(blind_rotate_ll_kernel, dim3((unsigned)n), dim3(kLlThreads), kLlLdsBytes, st, dd, (int)n,
-                           s.bk_ntt, s.tables512, steps, dump, s.tvs);
-    };
-    auto launch_ll2 = [&](const LinDesc* dd, size_t n, uint32_t* dump) {
-        // two rotations per workgroup: the row phase of one beside the inverse transforms of the other (kernels_ll.hip.h)
-        hipLaunchKernelGGL(blind_rotate_ll2_kernel, dim3((unsigned)((n + 1) / 2)), dim3(kLlThreads), kLl2LdsBytes, st, dd, (int)n,
-                           s.bk_ntt, s.tables512, steps, dump, s.fault, s.tvs);
-    };
-    auto launch_small = [&](const LinDesc* dd, size_t n, uint32_t* dump) {
-        if (g_ll2_threshold > 0 && (long)n <= g_ll2_threshold) {
-            launch_ll2(dd, n, dump);
-            return;
+    const plan::BrPlan p = plan::plan_blind_rotate(count, cus_of(s), g_tuning, g_br_shape);
+    for (int i = 0; i < p.n; i++) {
+        const plan::BrSegment& seg = p.seg[i];
+        const LinDesc* dd = d + seg.first;
+        uint32_t* dump = acc_dump ? acc_dump + seg.first * 2 * kN : nullptr;
+        const int n = (int)seg.count;
+        switch (seg.kernel) {
+            case plan::BrKernel::Batch:
+                hipLaunchKernelGGL(blind_rotate_kernel, dim3((unsigned)((seg.count + seg.active - 1) / seg.active)), dim3(kBrThreads), kBrLdsBytes, st,
+                                   dd, n, s.bk_ntt, s.tables_r4, steps, dump, seg.active, s.tvs);
+                break;
+            case plan::BrKernel::Ll:      // one 16-wave workgroup per rotation, transforms split in halves (kernels_ll.hip.h)
+                hipLaunchKernelGGL(blind_rotate_ll_kernel, dim3((unsigned)seg.count), dim3(kLlThreads), kLlLdsBytes, st,
+                                   dd, n, s.bk_ntt, s.tables512, steps, dump, s.tvs);
+                break;
+            case plan::BrKernel::Ll2:     // two rotations per workgroup: the row phase of one beside the inverse transforms of the other
+                hipLaunchKernelGGL(blind_rotate_ll2_kernel, dim3((unsigned)((seg.count + 1) / 2)), dim3(kLlThreads), kLl2LdsBytes, st,
+                                   dd, n, s.bk_ntt, s.tables512, steps, dump, s.fault, s.tvs);
+                break;
         }
-        if (g_ll2_threshold < 0 && auto_ll && auto_half && n > cu && n <= 6 * cu) {
-            // rounds of two rotations per CU on the paired kernel and a last started round of up to one per CU on the single one
-            const size_t rem = n % (2 * cu), paired = (rem == 0 || rem > cu) ? n : n - rem;
-            launch_ll2(dd, paired, dump);
-            if (paired < n) launch_ll(dd + paired, n - paired, dump ? dump + paired * 2 * kN : nullptr);
-            return;
-        }
-        if (auto_ll && auto_half && n > 4 * cu && n <= 5 * cu) {
-            // (without the paired kernel) four per CU at one rotation per SIMD (12.0 ms) and the rest on the low-latency kernel (3.2):
-            // 15.5 ms against 16.6 for five rounds of the low-latency kernel and 20 for a full round
-            launch_batch(dd, 4 * cu, kBrWavesPerBlock / 2, dump);
-            launch_ll(dd + 4 * cu, n - 4 * cu, dump ? dump + 4 * cu * 2 * kN : nullptr);
-            return;
-        }
-        const bool use_ll = auto_ll ? n <= 3 * cu : (long)n <= g_ll_threshold;
-        const bool use_half = auto_half ? n <= 4 * cu : (long)n <= g_half_threshold;
-        if (use_ll) {
-            launch_ll(dd, n, dump);
-        } else if (use_half) {
-            launch_batch(dd, n, kBrWavesPerBlock / 2, dump);
-        } else {
-            launch_batch(dd, n, kBrWavesPerBlock, dump);
-        }
-    };
-    if (g_br_shape > 0) {
-        // a caller that places launches itself (the two-lane scheduler, tools/two_lane_probe.py): the whole launch on one kernel
-        if (g_br_shape == 1) launch_batch(d, count, kBrWavesPerBlock, acc_dump);
-        else if (g_br_shape == 2) launch_ll2(d, count, acc_dump);
-        else launch_ll(d, count, acc_dump);
-        HIP_TRY(hipGetLastError());
-        return prof.commit();
-    }
-    const size_t tail = count % kRound;
-    const long tail_max = std::max(auto_half ? (long)(4 * cu) : g_half_threshold, auto_ll ? (long)((g_ll2_threshold < 0 ? 6 : 5) * cu) : g_ll_threshold);
-    if (g_tail_split && count > kRound && tail != 0 && (long)tail <= tail_max) {
-        const size_t full = count - tail;
-        launch_batch(d, full, kBrWavesPerBlock, acc_dump);
-        launch_small(d + full, tail, acc_dump ? acc_dump + full * 2 * kN : nullptr);
-    } else {
-        launch_small(d, count, acc_dump);
     }
     HIP_TRY(hipGetLastError());
     return prof.commit();
 }
+static_assert(plan::kBatchWaves == kBrWavesPerBlock && plan::kKsMaxPerWg == kKsWaves && kKsSplit == 8, "launch_plan.h plans for these kernels");
+// the key-switch plan of a path (launch_plan.h) over the shape S
+template <class S>
+plan::KsPlan plan_keyswitch_of(const DeviceState& s, size_t count, plan::KsRule rule)
+{
+    return plan::plan_keyswitch(count, cus_of(s), S::kn, KsDims<S>::min_slices, rule, g_tuning);
+}
 // keyswitch_kernel<S> over `ksk_padded` ([kn][t][2][row_pad] u32); *opted_in: the instantiation's dynamic-LDS opt-in on this device
 template <class S>
-int launch_keyswitch_shared(DeviceState& s, hipStream_t st, const typename S::Desc* d, size_t count, const uint32_t* ksk_padded, bool* opted_in)
+int launch_keyswitch_shared(DeviceState& s, hipStream_t st, const typename S::Desc* d, size_t count, const uint32_t* ksk_padded, bool* opted_in, const plan::KsPlan& p)
 {
     if (!*opted_in) {
         HIP_TRY(hipFuncSetAttribute((const void*)keyswitch_kernel<S>, hipFuncAttributeMaxDynamicSharedMemorySize, KsDims<S>::lds_bytes));
         *opted_in = true;
     }
-    int per_wg, slices;
-    ks_auto_shape(count, cus_of(s), S::kn, KsDims<S>::min_slices, &per_wg, &slices);
+    const int per_wg = p.per_wg, slices = p.slices;
     if (slices > 1) hipLaunchKernelGGL(keyswitch_zero_kernel<S>, dim3((unsigned)count), dim3(256), 0, st, d, (int)count);
     const unsigned ks_blocks = (unsigned)((count + per_wg - 1) / per_wg) * (unsigned)slices;
     hipLaunchKernelGGL(keyswitch_kernel<S>, dim3(ks_blocks), dim3(kKsThreads), KsDims<S>::lds_bytes, st, d, (int)count, ksk_padded, per_wg, slices);
@@ -528,14 +429,13 @@ int launch_keyswitch(DeviceState& s, hipStream_t st, const LinDesc* d, size_t co
     if (count == 0) return 0;
     ProfScope prof{s, st, count, true};
     if (int rc = prof.begin()) return rc;
-    const long split_max = g_ks_split_threshold < 0 ? ks_auto_split(cus_of(s)) : g_ks_split_threshold;
-    const long wg_max = g_ks_wg_threshold < 0 ? ks_auto_wg(cus_of(s)) : g_ks_wg_threshold;
-    if ((long)count <= split_max) {
+    const plan::KsPlan p = plan_keyswitch_of<KsShapeDefault>(s, count, plan::kKsDefaultPath);
+    if (p.kernel == plan::KsKernel::Split8) {
         launch_keyswitch_direct<KsShapeDefault, kKsSplit>(st, d, count, s.ksk);
-    } else if ((long)count <= wg_max) {
+    } else if (p.kernel == plan::KsKernel::WorkgroupPer) {
         launch_keyswitch_direct<KsShapeDefault, 1>(st, d, count, s.ksk);
     } else {
-        if (int rc = launch_keyswitch_shared<KsShapeDefault>(s, st, d, count, s.ksk, &s.ks_lds_opt_in)) return rc;
+        if (int rc = launch_keyswitch_shared<KsShapeDefault>(s, st, d, count, s.ksk, &s.ks_lds_opt_in, p)) return rc;
     }
     HIP_TRY(hipGetLastError());
     return prof.commit();
@@ -1800,18 +1700,20 @@ int cufhe_amd_set_option(const char* key, long value)
     if (!strcmp(key, "sched_affinity")) { g_sched_affinity = value != 0; return 0; }
     if (!strcmp(key, "sched_zero_copy")) { g_sched_zero_copy = value != 0; return 0; }
     if (!strcmp(key, "share_devices")) { g_share_devices = value; g_phys_count = cufhe_amd_device_count(); return 0; }
-    if (!strcmp(key, "ll_threshold")) { g_ll_threshold = value; return 0; }
-    if (!strcmp(key, "half_threshold")) { g_half_threshold = value; return 0; }
-    if (!strcmp(key, "tail_split")) { g_tail_split = value; return 0; }
+    // the launch-shape options that take any value (launch_plan.h); "ks_slices", "ks_per_wg" and "lvl2_kernel" check theirs below
+    static const struct { const char* key; long plan::Tuning::*field; } kPlanOptions[] = {
+        {"ll_threshold", &plan::Tuning::ll_threshold},   {"ll2_threshold", &plan::Tuning::ll2_threshold},
+        {"half_threshold", &plan::Tuning::half_threshold}, {"tail_split", &plan::Tuning::tail_split},
+        {"ks_wg_threshold", &plan::Tuning::ks_wg_threshold}, {"ks_split_threshold", &plan::Tuning::ks_split_threshold},
+        {"ps_batch_threshold", &plan::Tuning::ps_batch_threshold},
+    };
+    for (const auto& o : kPlanOptions)
+        if (!strcmp(key, o.key)) { g_tuning.*o.field = value; return 0; }
     if (!strcmp(key, "br_shape")) {
         if (value < 0 || value > 3) return fail(-1, "br_shape must be 0 (rules), 1 (batch kernel), 2 (paired low-latency kernel) or 3 (single)");
         g_br_shape = value;        // of the calling thread
         return 0;
     }
-    if (!strcmp(key, "ks_wg_threshold")) { g_ks_wg_threshold = value; return 0; }
-    if (!strcmp(key, "ks_split_threshold")) { g_ks_split_threshold = value; return 0; }
-    if (!strcmp(key, "ps_batch_threshold")) { g_ps_batch_threshold = value; return 0; }
-    if (!strcmp(key, "ll2_threshold")) { g_ll2_threshold = value; return 0; }
     if (!strcmp(key, "param_set") || !strcmp(key, "lvl0_param_set")) {
         if (value >= 0) {
             cufhe_amd_ps_params p;
@@ -1829,17 +1731,17 @@ int cufhe_amd_set_option(const char* key, long value)
     }
     if (!strcmp(key, "ks_slices")) {
         if (value != -1 && (value < 1 || value > 64 || (value & (value - 1)))) return fail(-1, "ks_slices must be -1 or a power of two 1..64");
-        g_ks_slices = value;
+        g_tuning.ks_slices = value;
         return 0;
     }
     if (!strcmp(key, "ks_per_wg")) {
         if (value != -1 && (value < 1 || value > 16)) return fail(-1, "ks_per_wg must be -1 or 1..16");
-        g_ks_per_wg = value;
+        g_tuning.ks_per_wg = value;
         return 0;
     }
     if (!strcmp(key, "lvl2_kernel")) {
         if (value < -1 || value > 1) return fail(-1, "lvl2_kernel must be -1 (by cost), 0 (eight half waves) or 1 (four quarter waves)");
-        g_lvl2_kernel = value;
+        g_tuning.lvl2_kernel = value;
         return 0;
     }
     if (!strcmp(key, "lvl0_ring")) {

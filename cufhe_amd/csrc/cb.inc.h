@@ -13,17 +13,13 @@ int cb_ready(const DeviceState& s, bool rotate)
     return 0;
 }
 
-// launch shape of private_keyswitch_kernel: tiles of kPksTile inputs share every key slice; when the tiles give fewer than four
-// workgroups per CU the i range is cut into slices (partial sums by vector atomics into a zeroed output)
+// private_keyswitch_kernel in the shape of plan::plan_private_keyswitch (launch_plan.h); slices add into a zeroed output
 int launch_private_keyswitch(DeviceState& s, hipStream_t st, const uint64_t* in, size_t count, uint32_t* out, int rows_per_out)
 {
     if (count == 0) return 0;
     ProfScope prof{s, st, count, true};
     if (int rc = prof.begin()) return rc;
-    const int tiles = (int)((count + kPksTile - 1) / kPksTile);
-    const long wgs = (long)tiles * 2 * kPksChunks;
-    const long want = 4L * (cus_of(s) > 0 ? cus_of(s) : 256);
-    int slices = wgs >= want ? 1 : (int)std::min<long>((want + wgs - 1) / wgs, (kPksIn + kPksIBlock - 1) / kPksIBlock);
+    const auto [tiles, slices] = plan::plan_private_keyswitch(count, cus_of(s), {kPksTile, kPksChunks, kPksIn, kPksIBlock});
     if (slices > 1)
         HIP_TRY(hipMemsetAsync(out, 0, (count / rows_per_out) * 2 * rows_per_out * kCbRowWords * sizeof(uint32_t), st));
     hipLaunchKernelGGL(private_keyswitch_kernel, dim3((unsigned)(tiles * 2 * kPksChunks), (unsigned)slices), dim3(kPksThreads), 0, st,

@@ -282,7 +282,7 @@ __device__ __forceinline__ void inverse_and_add(double (&A)[kRegs], uint32_t (&a
 // lock-step (one barrier per TRGSW row); waves past `count` only serve the row pipeline.
 // `active` (8 or 4) is the number of waves per workgroup that own a rotation: with 4, every SIMD
 // runs ONE rotation instead of two and a round of the grid takes about 11 ms instead of 19 -- the
-// shape for the tail of a launch that does not fill a second round (capi.hip: launch_blind_rotate).
+// shape for the tail of a launch that does not fill a second round (launch_plan.h: plan_blind_rotate).
 __global__ __launch_bounds__(kBrThreads, 2) void blind_rotate_kernel(
     const LinDesc* __restrict__ descs, int count, const double* __restrict__ bk_ntt,
     const NttTables* __restrict__ gt, int steps, uint32_t* __restrict__ acc_dump, int active, const uint32_t* __restrict__ tvs)

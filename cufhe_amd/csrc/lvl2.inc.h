@@ -67,8 +67,7 @@ int launch_blind_rotate_lvl2(DeviceState& s, hipStream_t st, const RotDesc2* d, 
     if (count == 0) return 0;
     ProfScope prof{s, st, count, false};
     if (int rc = prof.begin()) return rc;
-    const bool quarters = g_lvl2_kernel < 0 ? (long)count > (cus_of(s) > 0 ? cus_of(s) : 256) : g_lvl2_kernel == 1;
-    if (quarters) {
+    if (plan::lvl2_quarters(count, cus_of(s), g_tuning)) {
         // four quarter waves per rotation, two rotations per CU (kernels_lvl2q.hip.h)
         if (!s.br2q_lds_opt_in) {
             HIP_TRY(hipFuncSetAttribute((const void*)blind_rotate_lvl2q_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kQLdsBytes));
@@ -94,12 +93,11 @@ int launch_keyswitch_lvl2(DeviceState& s, hipStream_t st, const LinDesc64* d, si
     if (count == 0) return 0;
     ProfScope prof{s, st, count, true};
     if (int rc = prof.begin()) return rc;
-    // keyswitch_kernel over the lvl20 shape (j cut into runs that fill the CUs) at any count; keyswitch_direct_kernel with a
-    // workgroup per ciphertext (2.1 us per ciphertext) only by "ks_wg_threshold"
-    if (g_ks_wg_threshold > 0 && (long)count <= g_ks_wg_threshold) {
+    const plan::KsPlan p = plan_keyswitch_of<KsShapeLvl2>(s, count, plan::kKsFixedShapePath);
+    if (p.kernel == plan::KsKernel::WorkgroupPer) {
         launch_keyswitch_direct<KsShapeLvl2, 1>(st, d, count, s.ksk2);
     } else {
-        if (int rc = launch_keyswitch_shared<KsShapeLvl2>(s, st, d, count, s.ksk2, &s.ks2_lds_opt_in)) return rc;
+        if (int rc = launch_keyswitch_shared<KsShapeLvl2>(s, st, d, count, s.ksk2, &s.ks2_lds_opt_in, p)) return rc;
     }
     HIP_TRY(hipGetLastError());
     return prof.commit();

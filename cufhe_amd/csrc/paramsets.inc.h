@@ -8,12 +8,6 @@
 
 namespace {
 
-long g_ps_batch_threshold = -1;    // rotations per launch from which the wave-per-rotation kernel is used (-1: by cost)
-// By cost (tools/ps_latency.py, tools/ps_times.py; blind rotation + key switch, MI355X): the workgroup-per-rotation kernel takes
-// 4.3 / 3.4 / 3.7 ms per started round of one rotation per CU (default / k2n512 / cggi16; 4.2 / 3.0 / 3.5 for a few rotations), a round of the wave-per-rotation kernel
-// (up to eight per CU) 21 / 18.5 / 26 ms: the second wins from the fifth / sixth / seventh started round on (the seventh of cggi16: a tie).
-template <class PS> long ps_auto_batch(int cus) { return (PS::limbs > 1 ? 6L : PS::Nbit == 9 ? 5L : 4L) * std::max(1, cus) + 1; }
-
 struct PsState {
     bool ready = false, lds_opt_in = false, ks_lds_opt_in = false;
     double* bk_ntt = nullptr;
@@ -32,14 +26,10 @@ int ps_launch_keyswitch(DeviceState& s, PsState& ps, hipStream_t st, const LinDe
     if (count == 0) return 0;
     ProfScope prof{s, st, count, true};
     if (int rc = prof.begin()) return rc;
-    // keyswitch_kernel over the set's shape (j cut into runs that fill the CUs) at any count; the workgroup-per-ciphertext kernel
-    // only by "ks_wg_threshold" (or when the padded table could not be built)
-    if (ps.ksk_padded && !(g_ks_wg_threshold > 0 && (long)count <= g_ks_wg_threshold)) {
-        if constexpr (ps_ks_is_default_shape<PS>) {
-            if (int rc = launch_keyswitch_shared<KsShapeDefault>(s, st, d, count, ps.ksk_padded, &s.ks_lds_opt_in)) return rc;
-        } else {
-            if (int rc = launch_keyswitch_shared<KsShapePs<PS>>(s, st, d, count, ps.ksk_padded, &ps.ks_lds_opt_in)) return rc;
-        }
+    using Shape = std::conditional_t<ps_ks_is_default_shape<PS>, KsShapeDefault, KsShapePs<PS>>;
+    const plan::KsPlan p = plan_keyswitch_of<Shape>(s, count, plan::KsRule{false, ps.ksk_padded != nullptr});
+    if (p.kernel == plan::KsKernel::Shared) {
+        if (int rc = launch_keyswitch_shared<Shape>(s, st, d, count, ps.ksk_padded, ps_ks_is_default_shape<PS> ? &s.ks_lds_opt_in : &ps.ks_lds_opt_in, p)) return rc;
     } else {
         hipLaunchKernelGGL(keyswitch_ps_kernel<PS>, dim3((unsigned)count), dim3(kKsThreads), 0, st, d, (int)count, ps.ksk);
     }
@@ -88,7 +78,7 @@ int ps_launch_blind_rotate(DeviceState& s, PsState& ps, hipStream_t st, const Li
         HIP_TRY(hipFuncSetAttribute((const void*)blind_rotate_ps_batch_kernel<PS>, hipFuncAttributeMaxDynamicSharedMemorySize, PsbLds<PS>::bytes));
         ps.lds_opt_in = true;
     }
-    if ((long)count >= (g_ps_batch_threshold < 0 ? ps_auto_batch<PS>(cus_of(s)) : g_ps_batch_threshold)) {
+    if (plan::ps_use_batch(count, PS::limbs, PS::Nbit, cus_of(s), g_tuning)) {
         // one wave per rotation, 8 rotations per workgroup share the key rows (throughput shape)
         const unsigned blocks = (unsigned)((count + PsbLds<PS>::waves - 1) / PsbLds<PS>::waves);
         hipLaunchKernelGGL(blind_rotate_ps_batch_kernel<PS>, dim3(blocks), dim3(PsbLds<PS>::threads), PsbLds<PS>::bytes, st, d, (int)count,

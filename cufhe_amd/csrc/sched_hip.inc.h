@@ -66,14 +66,16 @@ class HipBackend : public sched::Backend {
         return n;
     }
     int num_streams() override { return (int)(g_sched_streams < 1 ? 1 : g_sched_streams); }
-    // one full-throughput round of the blind-rotate grid: a workgroup of 8 rotations per CU (capi.hip: launch_blind_rotate)
-    size_t round_gates() override
+    // the CU count the launch-shape rules go by (launch_plan.h; 0: unknown)
+    int cus() const
     {
         int cus = 0;
         if (g_cus_override > 0) cus = (int)g_cus_override;
         else if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, phys_device(device_)) != hipSuccess) { (void)hipGetLastError(); cus = 0; }
-        return (size_t)kBrWavesPerBlock * (size_t)(cus > 0 ? cus : 256);
+        return cus;
     }
+    // one full-throughput round of the blind-rotate grid: a workgroup of 8 rotations per CU
+    size_t round_gates() override { return (size_t)kBrWavesPerBlock * plan::device_cus(cus()); }
     int words(int level) override
     {
         if (g_param_set >= 0) return ps_ctxt_words((int)g_param_set, level);       // the active parameter set's sizes (2: a TRLWE, 3: a TRGSW in the NTT domain)
@@ -134,36 +136,10 @@ class HipBackend : public sched::Backend {
         if (level == 2) return keep(run_trlwe_ops(device_, (void*)st, g, n));
         return keep(::run_gates(device_, (void*)st, level, n, [&](size_t i) { return g[i]; }));
     }
-    // Two lanes: measured on MI355X with both lanes running (tools/two_lane_probe.py, profiles/r06_two_lane_probe.txt) -- a step of the
-    // paired low-latency kernel on half of the CUs, key switch included, 4.80 ms beside the bulk lane (4.59 alone); a chunk of the batch
-    // kernel on the other half 18.6 ms (17.9 alone).  Half of the CUs each: an in-order stream then never has more workgroups in flight
-    // than the other lane leaves free, so neither lane ever queues behind the other (full-width chunks beside the chain: 132 ms
-    // against 79).  Only for the hand-scheduled BASELINE path: the parameter-set and N = 2048 paths pick their own shapes.
-    bool lane_model(LaneModel* m) override
-    {
-        if (!g_sched_two_lane || g_param_set >= 0 || g_lvl0_ring != 1024) return false;
-        const size_t cus = round_gates() / kBrWavesPerBlock;
-        if (cus < 16) return false;
-        m->chain_gates = 2 * (cus / 2);
-        m->bulk_gates = (size_t)kBrWavesPerBlock * (cus / 2);
-        m->chain_ms = 4.80;
-        m->bulk_ms = 18.6;
-        return true;
-    }
-    // one dependence level of n rotations by the rules of launch_blind_rotate, key switch and launch gaps included (MI355X, ms)
-    double launch_ms(size_t n) override
-    {
-        if (n == 0) return 0.0;
-        const size_t c = std::max<size_t>(1, round_gates() / kBrWavesPerBlock), round = (size_t)kBrWavesPerBlock * c;
-        auto small = [&](size_t t) {
-            if (t <= c) return 3.1;
-            if (t > 6 * c) return 18.2;
-            const size_t rem = t % (2 * c), paired = (rem == 0 || rem > c) ? t : t - rem;
-            return (double)((paired + 2 * c - 1) / (2 * c)) * 5.0 + (paired < t ? 2.9 : 0.0);
-        };
-        const size_t full = n / round, tail = n % round;
-        return (double)full * 18.25 + (tail ? small(tail) : 0.0);      // tools/tail_times.py, gpurun_out/r06_tail_times_ks.txt
-    }
+    // the two-lane cost model of launch_plan.h.  Only for the hand-scheduled BASELINE path: the parameter-set and N = 2048 paths pick
+    // their own shapes.
+    bool lane_model(LaneModel* m) override { return g_sched_two_lane && g_param_set < 0 && g_lvl0_ring == 1024 && plan::lane_model(cus(), m); }
+    double launch_ms(size_t n) override { return plan::blind_rotate_ms(n, cus()); }
     int gate_weight(int op) override { return op == CUFHE_AMD_MUX || op == CUFHE_AMD_NMUX ? 2 : op == CUFHE_AMD_NOT || op == CUFHE_AMD_COPY ? 0 : 1; }
     bool shares_rotation(int op) override
     {
@@ -172,9 +148,7 @@ class HipBackend : public sched::Backend {
     }
     int run_gates_lane(int s, int level, const sched::GateRef* g, size_t n, int lane) override
     {
-        // chain lane: the paired low-latency kernel (the single one for at most a rotation per CU of its half); bulk lane: the batch kernel
-        const size_t cus = round_gates() / kBrWavesPerBlock;
-        g_br_shape = lane == 1 ? 1 : n <= cus / 2 ? 3 : 2;
+        g_br_shape = plan::lane_shape(lane, n, cus());
         const int rc = run_gates(s, level, g, n);
         g_br_shape = 0;
         return rc;

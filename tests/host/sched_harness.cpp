@@ -17,6 +17,7 @@
 #include <random>
 
 #include "../../cufhe_amd/csrc/sched_core.h"
+#include "../../cufhe_amd/csrc/launch_plan.h"
 
 using namespace cufhe_amd::sched;
 
@@ -695,25 +696,13 @@ class NullBackend : public Backend {
 };
 
 // The benchmark's dependent netlist (tools/bench_api.cpp: 256 x 16-bit ripple-carry adders, issued adder by adder) against a device
-// that does nothing but carries the HIP backend's cost model (sched_hip.inc.h: lane_model, launch_ms for 256 CUs): with
+// that does nothing but carries the HIP backend's cost model (launch_plan.h: lane_model, blind_rotate_ms for 256 CUs): with
 // CUFHE_AMD_SCHED_DEBUG=1 the scheduler prints what the level order and the two-lane plan are estimated to cost -- the plan can be
 // tuned here, on the CPU.
 class ModelBackend : public NullBackend {
    public:
-    bool lane_model(LaneModel* m) override { m->chain_gates = 256; m->bulk_gates = 1024; m->chain_ms = 4.80; m->bulk_ms = 18.6; return true; }
-    double launch_ms(size_t n) override
-    {
-        if (n == 0) return 0.0;
-        const size_t c = 256, round = 8 * c;
-        auto small = [&](size_t t) {
-            if (t <= c) return 3.1;
-            if (t > 6 * c) return 18.2;
-            const size_t rem = t % (2 * c), paired = (rem == 0 || rem > c) ? t : t - rem;
-            return (double)((paired + 2 * c - 1) / (2 * c)) * 5.0 + (paired < t ? 2.9 : 0.0);
-        };
-        const size_t full = n / round, tail = n % round;
-        return (double)full * 18.25 + (tail ? small(tail) : 0.0);
-    }
+    bool lane_model(LaneModel* m) override { return plan::lane_model(256, m); }
+    double launch_ms(size_t n) override { return plan::blind_rotate_ms(n, 256); }
     int gate_weight(int op) override { return op == 10 || op == 11 ? 2 : op == 12 || op == 13 ? 0 : 1; }
     uint64_t lanes[3] = {0, 0, 0};
     int run_gates_lane(int, int, const GateRef*, size_t, int lane) override { lanes[lane == 0 ? 0 : 1]++; return 0; }

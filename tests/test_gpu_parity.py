@@ -621,7 +621,7 @@ def test_ragged_batch_sizes(engine, keys, count):
                                         (2049, {}), (2700, {}), (4600, {})])                  # full rounds + a tail
 def test_launch_shapes_with_tails(engine, keys, count, opts):
     """Launches that do not fill whole rounds of the blind-rotate grid are cut into full rounds plus a
-    tail on a cheaper kernel (capi.hip, launch_blind_rotate): every output must still decrypt, sampled
+    tail on a cheaper kernel (launch_plan.h, plan_blind_rotate): every output must still decrypt, sampled
     outputs -- first, last, and both sides of every cut -- must be the oracle's words."""
     rng = np.random.default_rng(count)
     bits = rng.integers(0, 2, size=(2, count)).astype(np.uint8)
@@ -637,7 +637,7 @@ def test_launch_shapes_with_tails(engine, keys, count, opts):
         engine.api.set_option("ll_threshold", -1)
         engine.api.set_option("ll2_threshold", -1)
     assert np.array_equal(keys.decrypt(got, 0), 1 - bits[0] * bits[1])
-    # the cuts are in units of the device's CU count (capi.hip: launch_blind_rotate): a grid round is 8 rotations per CU
+    # the cuts are in units of the device's CU count (launch_plan.h: plan_blind_rotate): a grid round is 8 rotations per CU
     cus = engine.api.device_cus()
     cut = count - count % (8 * cus)
     idx = np.unique(np.clip(np.array([0, 3, 4, 7, cut - 1, cut, cut + 3, cut + 4, cut + 2 * cus - 1, cut + 2 * cus, cut + 2 * cus + 1, cut + 4 * cus - 1,

@@ -367,7 +367,7 @@ def test_ring_keyswitch_alone_4096(engine, ring, keys2, opts):
 # ---------------------------------------------------------------------------------------------------------------------------------
 # e. the other parameter sets
 # ---------------------------------------------------------------------------------------------------------------------------------
-PS_FACTOR = {"smallmod": 4, "k2n512": 5, "cggi16": 6}       # ps_auto_batch = factor x CUs + 1 rotations (include/cufhe_amd.h: 1025 / 1281 / 1537)
+PS_FACTOR = {"smallmod": 4, "k2n512": 5, "cggi16": 6}       # plan::ps_batch_from = factor x CUs + 1 rotations (include/cufhe_amd.h: 1025 / 1281 / 1537)
 
 
 @pytest.fixture(scope="module", params=list(PS_FACTOR))

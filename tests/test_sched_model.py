@@ -10,6 +10,7 @@ programs of tests/cpp/test_gate_api.cpp with their launch counts.
 """
 import json
 import os
+import shutil
 import subprocess
 
 import pytest
@@ -21,7 +22,7 @@ EXE = os.path.join(ROOT, "tests", "host", "sched_harness")
 
 @pytest.fixture(scope="module")
 def harness():
-    deps = [SRC, os.path.join(ROOT, "cufhe_amd", "csrc", "sched_core.h")]
+    deps = [SRC] + [os.path.join(ROOT, "cufhe_amd", "csrc", h) for h in ("sched_core.h", "launch_plan.h")]
     if not os.path.exists(EXE) or os.path.getmtime(EXE) < max(os.path.getmtime(d) for d in deps):
         subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-pthread", "-o", EXE, SRC])
     return EXE
@@ -143,6 +144,7 @@ def test_harness_notices_a_broken_scheduler(tmp_path, what, old, new, args):
     (tmp_path / "cufhe_amd" / "csrc").mkdir(parents=True)
     (tmp_path / "tests" / "host").mkdir(parents=True)
     (tmp_path / "cufhe_amd" / "csrc" / "sched_core.h").write_text(core.replace(old, new))
+    shutil.copy(os.path.join(ROOT, "cufhe_amd", "csrc", "launch_plan.h"), tmp_path / "cufhe_amd" / "csrc")      # the harness's cost model
     (tmp_path / "tests" / "host" / "sched_harness.cpp").write_text(open(SRC).read())
     exe = str(tmp_path / "mutant")
     subprocess.check_call(["g++", "-O1", "-std=c++17", "-pthread", "-o", exe, str(tmp_path / "tests" / "host" / "sched_harness.cpp")])

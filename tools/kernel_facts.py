@@ -36,7 +36,7 @@ KERNELS = {
     "blind_rotate_ps_batch_kernel<smallmod>": ("blind_rotate_ps_batch_kernel<cufhe_amd::PsSmallMod", (), 8, 8, 2, STEPS),
     "blind_rotate_ps_batch_kernel<k2n512>": ("blind_rotate_ps_batch_kernel<cufhe_amd::PsK2N512", (), 8, 8, 2, STEPS),
     "blind_rotate_ps_batch_kernel<cggi16>": ("blind_rotate_ps_batch_kernel<cufhe_amd::PsCggi16", (), 8, 8, 2, 500),
-    # units per workgroup: 16 for the launches of 4096 ciphertexts (capi.hip: ks_auto_shape); the smaller launches of the profiled
+    # units per workgroup: 16 for the launches of 4096 ciphertexts (launch_plan.h: plan_keyswitch); the smaller launches of the profiled
     # command fill the same grid with runs of j and are left out by their duration (main() below)
     "keyswitch_kernel": ("keyswitch_kernel<cufhe_amd::KsShapeDefault", (), 16, 16, 4, None),
     # the lvl20 shape always cuts j into at least two runs: 4096 ciphertexts are 512 workgroups of 16

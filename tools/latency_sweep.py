@@ -1,5 +1,5 @@
 """Gate-batch time by batch size and kernel choice (1 GPU): the numbers behind the launch-shape
-thresholds of cufhe_amd/csrc/capi.hip (launch_blind_rotate).  python tools/latency_sweep.py"""
+thresholds of cufhe_amd/csrc/launch_plan.h (plan_blind_rotate).  python tools/latency_sweep.py"""
 import os
 import sys
 import time
