@@ -40,6 +40,10 @@ class CbParams(ctypes.Structure):
                [("privksk_words", ctypes.c_uint64)]
 
 
+class PackParams(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_uint32) for k in ("n", "N", "t", "basebit")] + [("key_words", ctypes.c_uint64)]
+
+
 class Profile(ctypes.Structure):
     _fields_ = [("blind_rotate_ms", ctypes.c_double), ("blind_rotate_launches", ctypes.c_uint64),
                 ("blind_rotations", ctypes.c_uint64), ("keyswitch_ms", ctypes.c_double),
@@ -165,6 +169,9 @@ SIGNATURES = {
     "cufhe_amd_cb_rotate_batch": (ctypes.c_int, [ctypes.c_int, c_void, ctypes.c_size_t, c_void, c_void]),
     "cufhe_amd_private_keyswitch_batch": (ctypes.c_int, [ctypes.c_int, c_void, ctypes.c_size_t, c_void, c_void]),
     "cufhe_amd_circuit_bootstrap_batch": (ctypes.c_int, [ctypes.c_int, c_void, ctypes.c_size_t, c_void, c_void, c_void]),
+    "cufhe_amd_pack_get_params": (ctypes.c_int, [ctypes.POINTER(PackParams)]),
+    "cufhe_amd_pack_initialize": (ctypes.c_int, [c_void, ctypes.c_size_t]),
+    "cufhe_amd_pack_batch": (ctypes.c_int, [ctypes.c_int, c_void, ctypes.c_size_t, c_void, c_void, c_void, ctypes.c_size_t, c_void]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

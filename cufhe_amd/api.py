@@ -11,7 +11,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import lib, check, Params, Profile, Lvl2Params, SchedStats, PsParams, CbParams
+from ._lib import lib, check, Params, Profile, Lvl2Params, SchedStats, PsParams, CbParams, PackParams
 
 # op codes (include/cufhe_amd.h)
 NAND, NOR, XNOR, AND, OR, XOR, ANDNY, ANDYN, ORNY, ORYN, MUX, NMUX, NOT, COPY = range(14)
@@ -572,6 +572,52 @@ def circuit_bootstrap_batch(tlwe0, count, trgsw=None, trgsw_ntt=None, device=0, 
     """tlwe0 [count][n + 1] -> trgsw [count][(k + 1) l][k + 1][N] torus words and / or trgsw_ntt (NTT domain, doubles)"""
     check(lib.cufhe_amd_circuit_bootstrap_batch(device, stream, count, tlwe0.ptr, trgsw.ptr if trgsw is not None else None,
                                                 trgsw_ntt.ptr if trgsw_ntt is not None else None))
+
+
+# ---- TLWE packing: lvl0 TLWEs -> coefficients of a lvl1 TRLWE (INTEGRATION.md section 12) ----
+def pack_params():
+    p = PackParams()
+    check(lib.cufhe_amd_pack_get_params(ctypes.byref(p)))
+    return p
+
+
+def pack_initialize(key):
+    """key: the packing key lvl0 -> TRLWE, uint32 [n][t][2^basebit - 1][k + 1][N] (123.9 MB)"""
+    key = np.ascontiguousarray(key, dtype=np.uint32).ravel()
+    check(lib.cufhe_amd_pack_initialize(_ptr(key), key.size))
+
+
+def pack_batch(tlwe0, dst, pos, trlwe, count_in, count_out, device=0, stream=None):
+    """trlwe[o] = sum over the inputs m with dst[m] = o of X^pos[m] PackKS(tlwe0[m]); tlwe0 [count_in][n + 1], trlwe [count_out][2][N]
+    device buffers, dst / pos host integers"""
+    d, p = _i32(dst, count_in), _i32(pos, count_in)
+    check(lib.cufhe_amd_pack_batch(device, stream, count_in, tlwe0.ptr, _ptr(d), _ptr(p), count_out, trlwe.ptr))
+
+
+def gPackTLWEs(out_trlwe, ins, positions, st):
+    """out_trlwe (Trlwe) <- sum_m X^positions[m] PackKS(ins[m]) on device buffers: the stream is fenced first (cufhe_amd_stream_fence),
+    so the call runs behind the gates recorded on it and what is recorded afterwards runs behind the call; the inputs' device buffers
+    are gathered into one array by a Copy launch on the same stream."""
+    count = len(ins)
+    assert count == len(positions) and all(c.level == 0 for c in ins) and out_trlwe.level == 2
+    dev = st.device_id()
+    check(lib.cufhe_amd_stream_fence(dev, st.st()))
+    gathered = DeviceBuffer(max(count, 1) * LVL_WORDS[0], dev)
+    if count:
+        words = LVL_WORDS[0]
+        outs = (ctypes.c_void_p * count)(*[gathered.ptr + m * words * 4 for m in range(count)])
+        srcs = (ctypes.c_void_p * count)(*[lib.cufhe_amd_ctxt_device_ptr(c._h, dev) for c in ins])
+        ops = np.full(count, COPY, np.int32)
+        check(lib.cufhe_amd_gate_list(dev, st.st(), 0, count, _ptr(ops), outs, srcs, None, None))
+    pack_batch(gathered, np.zeros(count, np.int32), positions, _DevicePtr(lib.cufhe_amd_ctxt_device_ptr(out_trlwe._h, dev)), count, 1,
+               device=dev, stream=st.st())
+    check(lib.cufhe_amd_stream_synchronize(dev, st.st()))      # `gathered` is released on return
+    gathered.free()
+
+
+class _DevicePtr:
+    def __init__(self, ptr):
+        self.ptr = ptr
 
 
 def polymul512_batch(a, b, res, count, device=0, stream=None):

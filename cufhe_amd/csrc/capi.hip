@@ -27,6 +27,7 @@
 #include "kernels_lvl2q.hip.h"
 #include "kernels_ks2.hip.h"
 #include "kernels_pks.hip.h"
+#include "kernels_pack.hip.h"
 #define CUFHE_AMD_LL_DECLARATIONS_ONLY      // defined in kernels_ll.hip
 #include "kernels_ll.hip.h"
 #include "kernels_ps.hip.h"
@@ -87,6 +88,7 @@ struct DeviceState {
     bool br2q_lds_opt_in = false;
     uint32_t* ksk2 = nullptr;
     uint32_t* cb_pksk = nullptr;       // circuit bootstrapping: the private key-switching key lvl2 -> lvl1 (cb.inc.h)
+    uint32_t* pack_key = nullptr;      // TLWE packing: the lvl0 -> TRLWE key-switching key (pack.inc.h)
     std::vector<EventPair> br_events, ks_events;
     cufhe_amd_profile prof{};
     std::deque<PinnedBlock> staging;
@@ -980,6 +982,7 @@ int upload_ksk_padded(DevPtr<uint32_t>& d, const uint32_t* ksk, size_t rows, siz
 #include "sched_hip.inc.h"
 #include "lvl2.inc.h"
 #include "cb.inc.h"
+#include "pack.inc.h"
 #include "paramsets.inc.h"
 
 extern "C" {
@@ -1135,6 +1138,7 @@ int cufhe_amd_cleanup(void)
         ps_release(i);
         if (s.keys2_ready) { if (s.bk2_ntt) HIP_TRY(hipFree(s.bk2_ntt)); HIP_TRY(hipFree(s.bk2q_ntt)); HIP_TRY(hipFree(s.ksk2)); }
         if (s.cb_pksk) { HIP_TRY(hipFree(s.cb_pksk)); s.cb_pksk = nullptr; }
+        if (s.pack_key) { HIP_TRY(hipFree(s.pack_key)); s.pack_key = nullptr; }
         if (s.tables2) HIP_TRY(hipFree(s.tables2));
         if (s.tables2q) HIP_TRY(hipFree(s.tables2q));
         s.keys2_ready = s.br2_lds_opt_in = s.br2q_lds_opt_in = s.ks2_lds_opt_in = false;
@@ -1705,7 +1709,7 @@ int cufhe_amd_set_option(const char* key, long value)
         {"ll_threshold", &plan::Tuning::ll_threshold},   {"ll2_threshold", &plan::Tuning::ll2_threshold},
         {"half_threshold", &plan::Tuning::half_threshold}, {"tail_split", &plan::Tuning::tail_split},
         {"ks_wg_threshold", &plan::Tuning::ks_wg_threshold}, {"ks_split_threshold", &plan::Tuning::ks_split_threshold},
-        {"ps_batch_threshold", &plan::Tuning::ps_batch_threshold},
+        {"ps_batch_threshold", &plan::Tuning::ps_batch_threshold}, {"pack_slices", &plan::Tuning::pack_slices},
     };
     for (const auto& o : kPlanOptions)
         if (!strcmp(key, o.key)) { g_tuning.*o.field = value; return 0; }

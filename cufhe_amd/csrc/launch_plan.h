@@ -1,7 +1,8 @@
 // launch_plan.h -- every rule that cuts a batch into launches: which kernel, over which part of the batch, in which shape.
 // Host only, standard library only, no allocation: capi.hip and its .inc.h files turn the plans into launches, the scheduler's
 // backend (sched_hip.inc.h) prices its levels with the same plans, and tests/host/launch_plan_harness.cpp prints them on the CPU
-// (tests/test_launch_plan.py: the plans of the code this header replaced, tests/golden/launch_plans_v1.json).
+// (tests/test_launch_plan.py: the plans of the code this header replaced, tests/golden/launch_plans_v1.json; plan_pack:
+// tests/host/plan_pack_harness.cpp, tests/test_pack.py).
 //
 // Every rule is in units of the device's CU count (MI355X: 256; the measured milliseconds in the comments are that chip's).
 #pragma once
@@ -33,6 +34,7 @@ struct Tuning {
     // faster on the eight-wave kernel (256 rotations: 14.5 ms against 17.4), everything above on the four-wave one (512: 27.3 against 28.0,
     // 4096: 192 against 223)
     long lvl2_kernel = -1;
+    long pack_slices = -1;         // TLWE packing: slices of i per tile of inputs (plan_pack); -1 by the rule, else clamped to 1 .. max
 };
 
 // ---- blind rotation (kN = 1024, the default path) ----
@@ -242,6 +244,33 @@ inline PksPlan plan_private_keyswitch(size_t count, int cus, PksGeometry g)
     const long want = 4L * (long)device_cus(cus);
     if (wgs >= want || wgs == 0) return {tiles, 1};
     return {tiles, (int)std::min<long>((want + wgs - 1) / wgs, (g.in_words + g.i_block - 1) / g.i_block)};
+}
+
+// Launch shape of pack_keyswitch_kernel (kernels_pack.hip.h): `chunks` workgroups per tile of `tile` inputs (one per 256 of the 2N row
+// words); as for the private key switch, tiles that give fewer than four workgroups per CU cut the i range (`in_words`, staged `i_block`
+// at a time) into slices.  Every workgroup adds into the zeroed outputs with vector atomics at any shape, so the words do not depend
+// on it.  grid_x = chunks * tiles (tile = blockIdx.x % tiles), grid_y = slices.
+struct PackGeometry { int tile, chunks, in_words, i_block; };
+struct PackPlan { int tiles, slices; unsigned grid_x, grid_y; };
+constexpr int pack_max_slices(PackGeometry g) { return (g.in_words + g.i_block - 1) / g.i_block; }
+// inputs [first, first + n) of tile `tile`; words [begin, end) of slice `slice` (empty for the last slices when `slices` does not
+// divide the range evenly): the kernel and tests/host/plan_pack_harness.cpp both read the plan through these
+constexpr long pack_tile_first(int tile, int tile_size) { return (long)tile * tile_size; }
+constexpr int pack_tile_inputs(int tile, int tile_size, long count) { return (int)(count - pack_tile_first(tile, tile_size) < tile_size ? count - pack_tile_first(tile, tile_size) : tile_size); }
+constexpr int pack_slice_begin(int slice, int slices, int in_words)
+{
+    return (in_words + slices - 1) / slices * slice < in_words ? (in_words + slices - 1) / slices * slice : in_words;
+}
+inline PackPlan plan_pack(size_t count, int cus, PackGeometry g, const Tuning& t)
+{
+    const int tiles = (int)((count + g.tile - 1) / g.tile), max_slices = pack_max_slices(g);
+    const long wgs = (long)tiles * g.chunks;
+    const long want = 4L * (long)device_cus(cus);
+    long slices = 1;
+    if (t.pack_slices > 0) slices = t.pack_slices;
+    else if (wgs > 0 && wgs < want) slices = (want + wgs - 1) / wgs;
+    slices = std::max(1L, std::min<long>(slices, max_slices));
+    return {tiles, (int)slices, (unsigned)wgs, (unsigned)slices};
 }
 
 }  // namespace plan

@@ -479,6 +479,34 @@ int cufhe_amd_private_keyswitch_batch(int device, void* stream, size_t count, co
  * (may be NULL): the words cufhe_amd_trgsw_to_ntt_batch makes of trgsw */
 int cufhe_amd_circuit_bootstrap_batch(int device, void* stream, size_t count, const uint32_t* tlwe0, uint32_t* trgsw, double* trgsw_ntt);
 
+/* ---- TLWE packing: lvl0 ciphertexts into coefficients of a lvl1 TRLWE (no counterpart in the reference) ----
+ * The way back from gate results to a packed word: the packed TRLWE can be the data operand of cufhe_amd_cmux_batch / _cmux_rotate_batch
+ * (a RAM write, a table built on the device).  One exact table-sum key switch with a rotation at write-out, integer arithmetic mod 2^32
+ * only.  With abar_i = a_i + 2^15 and a_ij = (abar_i >> (32 - 2 (j+1))) & 3 (t = 8 unsigned digits of basebit = 2: the library's own
+ * numbers, reported by cufhe_amd_pack_get_params) for a lvl0 TLWE x = (a_0 .. a_{n-1}, b):
+ *     PackKS(x) = (0, b X^0) - sum_i sum_j [a_ij != 0] K[i][j][a_ij - 1]                  a TRLWE [2][N], the a polynomial first
+ *     out[o]    = sum over the inputs m with dst[m] = o of X^pos[m] PackKS(in[m])          X^e: the negacyclic product of section 11
+ * An output no input names is the zero TRLWE; inputs at the same position of the same output add; all count_out outputs are written.
+ * K is the caller's key, [n][t][2^basebit - 1][k+1][N] uint32 (30 965 760 words, 123.9 MB, on every device of SetGPUNum):
+ * K[i][j][v-1] = TRLWE_s1(v * s0_i * 2^(32 - 2 (j+1))), a constant message, phase b - a s.  The library does not generate it.
+ * Default parameter set only ("param_set" active: -1).  There is no recorded form: cufhe_amd_stream_fence orders a call behind the
+ * gates recorded on its stream. */
+typedef struct cufhe_amd_pack_params {
+    uint32_t n, N;                     /* input lvl0 dimension, output ring */
+    uint32_t t, basebit;               /* 8 unsigned digits of 2 bits */
+    uint64_t key_words;                /* n t (2^basebit - 1) (k+1) N uint32 */
+} cufhe_amd_pack_params;
+int cufhe_amd_pack_get_params(cufhe_amd_pack_params* out);
+/* key: host words as above, copied to every device of SetGPUNum through pinned chunks (build first, swap last: a failure leaves the key
+ * loaded before in use).  -1: null pointer, wrong size, "param_set" active. */
+int cufhe_amd_pack_initialize(const uint32_t* key, size_t words);
+/* tlwe0[count_in][n+1] and trlwe[count_out][2][N] on the device; dst and pos HOST arrays of count_in entries (staged through the stream's
+ * workspace like the exponents of section 11).  Refused before any device work: -1 for a null pointer, dst outside [0, count_out),
+ * pos outside [0, N) or "param_set" active; -3 without cufhe_amd_pack_initialize.  "pack_slices" (cufhe_amd_set_option, default -1 =
+ * by the rule of plan_pack) forces the number of slices the lvl0 words are cut into; the words do not depend on the shape. */
+int cufhe_amd_pack_batch(int device, void* stream, size_t count_in, const uint32_t* tlwe0, const int32_t* dst, const int32_t* pos,
+                         size_t count_out, uint32_t* trlwe);
+
 /* ---- other parameter sets (CMakeLists.txt:8-24: USE_80BIT_SECURITY / USE_CGGI19 / USE_CONCRETE select TFHEpp
  * parameter headers at build time; k > 1: src/bootstrap_gpu.cu:402-421; N = 512: include/ntt_gpu/ntt_gpuntt.cuh:283-329)
  * Every set of cufhe_amd/csrc/kernels_ps.hip.h is compiled in and chosen by index: 0 = the default set (the same

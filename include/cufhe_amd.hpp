@@ -566,6 +566,36 @@ inline void gCircuitBootstrapping(cuFHETRGSWNTTlvl1& out, Ctxt<TFHEpp::lvl0param
     CUFHE_AMD_CHECK(cufhe_amd_enqueue_trlwe_op(st.device_id(), st.raw(), CUFHE_AMD_TL_CIRCUIT_BOOTSTRAP, 0, out.handle, in.handle));
 }
 #endif  // CUFHE_AMD_SMALL_NTT_MODULUS
+/// TLWE packing (include/cufhe_amd.h, cufhe_amd_pack_batch): lvl0 ciphertexts -- the results of gates --
+/// become coefficients of one TRLWE, the data operand of gCMUXNTT / gCMUXRotateNTT.  The packing key is the caller's,
+/// [n][8][3][k + 1][N] uint32 words (123.9 MB), loaded once on every device of SetGPUNum.  Default parameter set only.
+inline void InitializePacking(const uint32_t* key, size_t words) { CUFHE_AMD_CHECK(cufhe_amd_pack_initialize(key, words)); }
+/// out = sum_m X^pos[m] PackKS(*ins[m]) on device buffers.  Not recorded: the stream is fenced first, as Stream::st() does, so the
+/// call runs behind the gates recorded on `st` and what is recorded on `st` afterwards runs behind it; the inputs' own device
+/// buffers are gathered into one array by a Copy launch on the same stream.  Returns when the packed TRLWE is in out's device buffer.
+inline void gPackTLWEs(cuFHETRLWElvl1& out, const std::vector<Ctxt<TFHEpp::lvl0param>*>& ins, const std::vector<int>& pos, Stream st)
+{
+    if (ins.size() != pos.size()) CUFHE_AMD_CHECK(-1);
+    const int dev = st.device_id();
+    const size_t count = ins.size(), words = (size_t)cufhe_amd_ctxt_words(0);
+    CUFHE_AMD_CHECK(cufhe_amd_stream_fence(dev, st.raw()));
+    void* gathered = nullptr;
+    CUFHE_AMD_CHECK(cufhe_amd_malloc(dev, (count ? count : 1) * words * sizeof(uint32_t), &gathered));
+    std::vector<int32_t> ops(count, (int32_t)CUFHE_AMD_COPY), dst(count, 0), p(pos.begin(), pos.end());
+    std::vector<uint32_t*> rows(count);
+    std::vector<const uint32_t*> srcs(count);
+    for (size_t m = 0; m < count; m++) {
+        rows[m] = static_cast<uint32_t*>(gathered) + m * words;
+        srcs[m] = cufhe_amd_ctxt_device_ptr(ins[m]->handle, dev);
+    }
+    int rc = count ? cufhe_amd_gate_list(dev, st.raw(), 0, count, ops.data(), rows.data(), srcs.data(), nullptr, nullptr) : 0;
+    if (rc >= 0)
+        rc = cufhe_amd_pack_batch(dev, st.raw(), count, static_cast<const uint32_t*>(gathered), dst.data(), p.data(), 1,
+                                  cufhe_amd_ctxt_device_ptr(out.handle, dev));
+    if (rc >= 0) rc = cufhe_amd_stream_synchronize(dev, st.raw());
+    (void)cufhe_amd_free(dev, gathered);
+    CUFHE_AMD_CHECK(rc);
+}
 
 #undef CUFHE_AMD_GATE1
 #undef CUFHE_AMD_GATE2
