@@ -172,6 +172,11 @@ SIGNATURES = {
     "cufhe_amd_pack_get_params": (ctypes.c_int, [ctypes.POINTER(PackParams)]),
     "cufhe_amd_pack_initialize": (ctypes.c_int, [c_void, ctypes.c_size_t]),
     "cufhe_amd_pack_batch": (ctypes.c_int, [ctypes.c_int, c_void, ctypes.c_size_t, c_void, c_void, c_void, ctypes.c_size_t, c_void]),
+    "cufhe_amd_lut_rotate_batch": (ctypes.c_int, [ctypes.c_int, c_void, ctypes.c_size_t, c_void, c_void, ctypes.c_size_t, c_void, ctypes.c_int,
+                                                  ctypes.c_int, c_void]),
+    "cufhe_amd_lut_lookup_batch": (ctypes.c_int, [ctypes.c_int, c_void, ctypes.c_size_t, c_void, c_void, ctypes.c_size_t, c_void, ctypes.c_int,
+                                                  c_void]),
+    "cufhe_amd_trlwe_spread_batch": (ctypes.c_int, [ctypes.c_int, c_void, ctypes.c_size_t, c_void, ctypes.c_int, ctypes.c_int, c_void]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

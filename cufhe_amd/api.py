@@ -620,6 +620,68 @@ class _DevicePtr:
         self.ptr = ptr
 
 
+# ---- encrypted-table lookup: blind rotation from a caller's TRLWE ----
+def lut_rotate_batch(tlwe0, tables, acc, count, table_count, src=None, nout=1, steps=-1, device=0, stream=None):
+    """acc[g] = LutRotate(tables[src[g]], tlwe0[g], log2 nout) after `steps` CMux steps (< 0: all n): the blind rotation whose initial
+    accumulator is X^bbar times the TRLWE tables[src[g]] (src None: g).  tlwe0 [count][n + 1], tables [table_count][2][N], acc
+    [count][2][N] device buffers; src host integers."""
+    s = _i32(src, count) if src is not None else None
+    check(lib.cufhe_amd_lut_rotate_batch(device, stream, count, tlwe0.ptr, tables.ptr, table_count, _ptr(s), int(nout), int(steps), acc.ptr))
+
+
+def lut_lookup_batch(tlwe0, tables, out, count, table_count, src=None, nout=1, device=0, stream=None):
+    """out[g][j] = KeySwitch(SampleExtract(j)(LutRotate(tables[src[g]], tlwe0[g]))), j < nout: lvl0 TLWEs [count][nout][n + 1]"""
+    s = _i32(src, count) if src is not None else None
+    check(lib.cufhe_amd_lut_lookup_batch(device, stream, count, tlwe0.ptr, tables.ptr, table_count, _ptr(s), int(nout), out.ptr))
+
+
+def trlwe_spread_batch(inp, out, count, stride, reps, device=0, stream=None):
+    """out[g] = X^(-stride (reps // 2)) sum_{i < reps} X^(i stride) inp[g] on TRLWEs [count][2][N]; out must not overlap inp"""
+    check(lib.cufhe_amd_trlwe_spread_batch(device, stream, count, inp.ptr, int(stride), int(reps), out.ptr))
+
+
+def _ctxt_ptr(c, dev):
+    return _DevicePtr(lib.cufhe_amd_ctxt_device_ptr(c._h, dev))
+
+
+def gBlindRotateTRLWE(out_trlwe, table, addr, st, nout=1):
+    """out_trlwe (Trlwe) <- LutRotate(table, addr, log2 nout) on device buffers: table a Trlwe, addr a level-0 Ctxt.  Not recorded: the
+    stream is fenced first (cufhe_amd_stream_fence), so the call runs behind the gates recorded on it and what is recorded afterwards
+    runs behind the call.  out_trlwe must not be table."""
+    assert out_trlwe.level == 2 and table.level == 2 and addr.level == 0
+    dev = st.device_id()
+    check(lib.cufhe_amd_stream_fence(dev, st.st()))
+    lut_rotate_batch(_ctxt_ptr(addr, dev), _ctxt_ptr(table, dev), _ctxt_ptr(out_trlwe, dev), 1, 1, nout=nout, device=dev, stream=st.st())
+
+
+def gLookupTRLWE(outs, table, addr, st):
+    """outs[j] (level-0 Ctxts, 1, 2, 4 or 8 of them) <- output j of the lookup of `table` (Trlwe) at the encrypted address `addr`, on
+    device buffers; fenced like gBlindRotateTRLWE.  The outputs are computed into one array and scattered to the objects' device
+    buffers by a Copy launch on the same stream."""
+    outs = list(outs)
+    nout = len(outs)
+    assert table.level == 2 and addr.level == 0 and all(o.level == 0 for o in outs)
+    dev = st.device_id()
+    check(lib.cufhe_amd_stream_fence(dev, st.st()))
+    words = LVL_WORDS[0]
+    res = DeviceBuffer(max(nout, 1) * words, dev)
+    lut_lookup_batch(_ctxt_ptr(addr, dev), _ctxt_ptr(table, dev), res, 1, 1, nout=nout, device=dev, stream=st.st())
+    dsts = (ctypes.c_void_p * nout)(*[lib.cufhe_amd_ctxt_device_ptr(o._h, dev) for o in outs])
+    srcs = (ctypes.c_void_p * nout)(*[res.ptr + j * words * 4 for j in range(nout)])
+    ops = np.full(nout, COPY, np.int32)
+    check(lib.cufhe_amd_gate_list(dev, st.st(), 0, nout, _ptr(ops), dsts, srcs, None, None))
+    check(lib.cufhe_amd_stream_synchronize(dev, st.st()))      # `res` is released on return
+    res.free()
+
+
+def gSpreadTRLWE(out, inp, stride, reps, st):
+    """out (Trlwe) <- Spread(inp, stride, reps) on device buffers; fenced like gBlindRotateTRLWE.  out must not be inp."""
+    assert out.level == 2 and inp.level == 2
+    dev = st.device_id()
+    check(lib.cufhe_amd_stream_fence(dev, st.st()))
+    trlwe_spread_batch(_ctxt_ptr(inp, dev), _ctxt_ptr(out, dev), 1, stride, reps, device=dev, stream=st.st())
+
+
 def polymul512_batch(a, b, res, count, device=0, stream=None):
     check(lib.cufhe_amd_polymul512_batch(device, stream, count, a.ptr, b.ptr, res.ptr))
 

@@ -28,6 +28,7 @@
 #include "kernels_ks2.hip.h"
 #include "kernels_pks.hip.h"
 #include "kernels_pack.hip.h"
+#include "kernels_lut.hip.h"
 #define CUFHE_AMD_LL_DECLARATIONS_ONLY      // defined in kernels_ll.hip
 #include "kernels_ll.hip.h"
 #include "kernels_ps.hip.h"
@@ -363,15 +364,21 @@ struct ProfScope {
     }
 };
 
-int launch_blind_rotate(DeviceState& s, hipStream_t st, const LinDesc* d, size_t count, int steps, uint32_t* acc_dump)
+// tables (optional, a device array parallel to d): rotation g starts from X^bbar times the TRLWE tables[g] instead of its descriptor's
+// test vector (cufhe_amd_lut_*_batch, lut.inc.h), on the <true> instantiations of the same three kernels; nullptr: every other launch
+int launch_blind_rotate(DeviceState& s, hipStream_t st, const LinDesc* d, size_t count, int steps, uint32_t* acc_dump,
+                        const uint32_t* const* tables)
 {
     if (count == 0) return 0;
     ProfScope prof{s, st, count, false};
     if (int rc = prof.begin()) return rc;
     if (!s.br_lds_opt_in) {      // > 64 KiB of dynamic LDS needs an opt-in, per device
-        HIP_TRY(hipFuncSetAttribute((const void*)blind_rotate_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kBrLdsBytes));
-        HIP_TRY(hipFuncSetAttribute((const void*)blind_rotate_ll_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kLlLdsBytes));
-        HIP_TRY(hipFuncSetAttribute((const void*)blind_rotate_ll2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kLl2LdsBytes));
+        HIP_TRY(hipFuncSetAttribute((const void*)blind_rotate_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, kBrLdsBytes));
+        HIP_TRY(hipFuncSetAttribute((const void*)blind_rotate_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, kBrLdsBytes));
+        HIP_TRY(hipFuncSetAttribute((const void*)blind_rotate_ll_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, kLlLdsBytes));
+        HIP_TRY(hipFuncSetAttribute((const void*)blind_rotate_ll_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, kLlLdsBytes));
+        HIP_TRY(hipFuncSetAttribute((const void*)blind_rotate_ll2_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, kLl2LdsBytes));
+        HIP_TRY(hipFuncSetAttribute((const void*)blind_rotate_ll2_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, kLl2LdsBytes));
         s.br_lds_opt_in = true;
     }
     const plan::BrPlan p = plan::plan_blind_rotate(count, cus_of(s), g_tuning, g_br_shape);
@@ -379,19 +386,21 @@ int launch_blind_rotate(DeviceState& s, hipStream_t st, const LinDesc* d, size_t
         const plan::BrSegment& seg = p.seg[i];
         const LinDesc* dd = d + seg.first;
         uint32_t* dump = acc_dump ? acc_dump + seg.first * 2 * kN : nullptr;
+        const uint32_t* const* tt = tables ? tables + seg.first : nullptr;
         const int n = (int)seg.count;
+        const dim3 batch_grid((unsigned)((seg.count + seg.active - 1) / seg.active)), ll_grid((unsigned)seg.count), ll2_grid((unsigned)((seg.count + 1) / 2));
         switch (seg.kernel) {
             case plan::BrKernel::Batch:
-                hipLaunchKernelGGL(blind_rotate_kernel, dim3((unsigned)((seg.count + seg.active - 1) / seg.active)), dim3(kBrThreads), kBrLdsBytes, st,
-                                   dd, n, s.bk_ntt, s.tables_r4, steps, dump, seg.active, s.tvs);
+                hipLaunchKernelGGL(tt ? blind_rotate_kernel<true> : blind_rotate_kernel<false>, batch_grid, dim3(kBrThreads), kBrLdsBytes, st,
+                                   dd, n, s.bk_ntt, s.tables_r4, steps, dump, seg.active, s.tvs, tt);
                 break;
             case plan::BrKernel::Ll:      // one 16-wave workgroup per rotation, transforms split in halves (kernels_ll.hip.h)
-                hipLaunchKernelGGL(blind_rotate_ll_kernel, dim3((unsigned)seg.count), dim3(kLlThreads), kLlLdsBytes, st,
-                                   dd, n, s.bk_ntt, s.tables512, steps, dump, s.tvs);
+                hipLaunchKernelGGL(tt ? blind_rotate_ll_kernel<true> : blind_rotate_ll_kernel<false>, ll_grid, dim3(kLlThreads), kLlLdsBytes, st,
+                                   dd, n, s.bk_ntt, s.tables512, steps, dump, s.tvs, tt);
                 break;
             case plan::BrKernel::Ll2:     // two rotations per workgroup: the row phase of one beside the inverse transforms of the other
-                hipLaunchKernelGGL(blind_rotate_ll2_kernel, dim3((unsigned)((seg.count + 1) / 2)), dim3(kLlThreads), kLl2LdsBytes, st,
-                                   dd, n, s.bk_ntt, s.tables512, steps, dump, s.fault, s.tvs);
+                hipLaunchKernelGGL(tt ? blind_rotate_ll2_kernel<true> : blind_rotate_ll2_kernel<false>, ll2_grid, dim3(kLlThreads), kLl2LdsBytes, st,
+                                   dd, n, s.bk_ntt, s.tables512, steps, dump, s.fault, s.tvs, tt);
                 break;
         }
     }
@@ -879,7 +888,7 @@ struct BasePath {
     static constexpr auto se_kernel = sample_extract_desc_kernel;
     DeviceState& s;
     int ready() const { return s.keys_ready ? 0 : fail(-3, "Initialize(ek) has not been called for this device"); }
-    int rotate(hipStream_t st, const LinDesc* d, size_t count, int steps, uint32_t* dump) const { return launch_blind_rotate(s, st, d, count, steps, dump); }
+    int rotate(hipStream_t st, const LinDesc* d, size_t count, int steps, uint32_t* dump) const { return launch_blind_rotate(s, st, d, count, steps, dump, nullptr); }
     int keyswitch(hipStream_t st, const LinDesc* d, size_t count) const { return launch_keyswitch(s, st, d, count); }
     // one wave per descriptor, kNttWavesPerBlock of them beside the workgroup's copy of the tables: both CMUX kernels
     template <class Desc>
@@ -983,6 +992,7 @@ int upload_ksk_padded(DevPtr<uint32_t>& d, const uint32_t* ksk, size_t rows, siz
 #include "lvl2.inc.h"
 #include "cb.inc.h"
 #include "pack.inc.h"
+#include "lut.inc.h"
 #include "paramsets.inc.h"
 
 extern "C" {
@@ -1390,7 +1400,7 @@ int cufhe_amd_bootstrap_batch(int device, void* stream, size_t count, uint32_t* 
     LinDesc *drot, *dks;
     if (int rc = upload_descs(s, sc, rot, &drot)) return rc;
     if (int rc = upload_descs(s, sc, ks, &dks)) return rc;
-    if (int rc = launch_blind_rotate(s, st, drot, count, kLvl0N, nullptr)) return rc;
+    if (int rc = launch_blind_rotate(s, st, drot, count, kLvl0N, nullptr, nullptr)) return rc;
     return launch_keyswitch(s, st, dks, count);
 }
 
@@ -1403,7 +1413,7 @@ int cufhe_amd_blind_rotate_batch(int device, void* stream, size_t count, const u
     if (steps < 0 || steps > kLvl0N) steps = kLvl0N;
     hipStream_t st = (hipStream_t)stream;
     return direct_batch(s, st, count, [&](size_t g) { return LinDesc{tlwe0 + g * kLvl0Words, tlwe0 + g * kLvl0Words, nullptr, 1, 0, 0u, 0u}; },
-                        [&](const LinDesc* d) { return launch_blind_rotate(s, st, d, count, steps, acc); });
+                        [&](const LinDesc* d) { return launch_blind_rotate(s, st, d, count, steps, acc, nullptr); });
 }
 
 int cufhe_amd_keyswitch_batch(int device, void* stream, size_t count, const uint32_t* tlwe1, uint32_t* tlwe0)

@@ -283,9 +283,15 @@ __device__ __forceinline__ void inverse_and_add(double (&A)[kRegs], uint32_t (&a
 // `active` (8 or 4) is the number of waves per workgroup that own a rotation: with 4, every SIMD
 // runs ONE rotation instead of two and a round of the grid takes about 11 ms instead of 19 -- the
 // shape for the tail of a launch that does not fill a second round (launch_plan.h: plan_blind_rotate).
+// TABLE (launch_blind_rotate with a table array): rotation g names the TRLWE tables[g] = (A, B) of 2N words
+// and its initial accumulator is X^bbar (A, B) instead of (0, X^bbar TV); its descriptor carries only the output shift (pad = s << 8,
+// no test-vector row).  A null entry keeps the descriptor's own test vector.  A compile-time switch of the prologue: every launch
+// without tables runs the <false> instantiation, whose code is the kernel as it was.
+template <bool TABLE>
 __global__ __launch_bounds__(kBrThreads, 2) void blind_rotate_kernel(
     const LinDesc* __restrict__ descs, int count, const double* __restrict__ bk_ntt,
-    const NttTables* __restrict__ gt, int steps, uint32_t* __restrict__ acc_dump, int active, const uint32_t* __restrict__ tvs)
+    const NttTables* __restrict__ gt, int steps, uint32_t* __restrict__ acc_dump, int active, const uint32_t* __restrict__ tvs,
+    const uint32_t* const* __restrict__ tables)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     double* tabs = (double*)(smem + kBrLdsTables);
@@ -330,7 +336,21 @@ __global__ __launch_bounds__(kBrThreads, 2) void blind_rotate_kernel(
         const bool neg = (bbar != 2 * kN) && ((e < (bbar & (kN - 1))) != ((bbar >> kNbit) != 0));
         acc1[r] = neg ? 0u - kMu : kMu;
     }
-    if (d.pad) {              // a user gate: X^bbar times its test vector instead, 16 coefficients per lane gathered once
+    const uint32_t* tab = nullptr;
+    if constexpr (TABLE) tab = tables[g];       // a null entry: the descriptor's own test vector, as without TABLE
+    if (TABLE && tab) {       // X^bbar (A, B) of the rotation's table, both polynomials gathered like a test vector
+        const int s = desc_shift(d.pad);
+        uint32_t bb = bbar;
+        if (s) {
+            for (int i = lane; i < kLvl0N; i += 64) abar_lds[i] = (uint16_t)ms_abar((uint32_t)d.ca * d.in0[i] + (uint32_t)d.cb * d.in1[i], s);
+            bb = ms_bbar(bword, s);
+        }
+#pragma unroll
+        for (int r = 0; r < kRegs; r++) {
+            acc0[r] = rotated_tv_coef(tab, bb, lane + 64 * r);
+            acc1[r] = rotated_tv_coef(tab + kN, bb, lane + 64 * r);
+        }
+    } else if (d.pad) {       // a user gate: X^bbar times its test vector instead, 16 coefficients per lane gathered once
         const uint32_t* tv = desc_tv(tvs, d.pad);
         const int s = desc_shift(d.pad);
         uint32_t bb = bbar;

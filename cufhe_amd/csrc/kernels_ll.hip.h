@@ -40,9 +40,22 @@ constexpr int kLlDigBytes = 2 * kN * 4;                                       //
 constexpr int kLlLdsAbar = kLlLdsDig + kLlDigBytes;                           // + 8192
 constexpr int kLlLdsBytes = kLlLdsAbar + kAbarBytes + 16;                     // 147472
 
+// TABLE (launch_blind_rotate with a table array): the rotation starts from (X^bbar A, X^bbar B) of the TRLWE
+// tables[g] (2N words; a null entry: the descriptor's test vector) instead of (0, X^bbar TV).  A compile-time switch of the prologue;
+// both instantiations are compiled in kernels_ll.hip.
+template <bool TABLE>
 __global__ __launch_bounds__(kLlThreads) void blind_rotate_ll_kernel(
     const LinDesc* __restrict__ descs, int count, const double* __restrict__ bk_ntt,
-    const Ntt512Tables* __restrict__ gt2, int steps, uint32_t* __restrict__ acc_dump, const uint32_t* __restrict__ tvs);
+    const Ntt512Tables* __restrict__ gt2, int steps, uint32_t* __restrict__ acc_dump, const uint32_t* __restrict__ tvs,
+    const uint32_t* const* __restrict__ tables);
+#define CUFHE_AMD_LL_INSTANCE(T)                                                                                                  \
+    template __global__ void blind_rotate_ll_kernel<T>(const LinDesc* __restrict__, int, const double* __restrict__,              \
+                                                       const Ntt512Tables* __restrict__, int, uint32_t* __restrict__,             \
+                                                       const uint32_t* __restrict__, const uint32_t* const* __restrict__);
+#ifdef CUFHE_AMD_LL_DECLARATIONS_ONLY
+extern CUFHE_AMD_LL_INSTANCE(false)
+extern CUFHE_AMD_LL_INSTANCE(true)
+#endif
 #ifndef CUFHE_AMD_LL_DECLARATIONS_ONLY
 // The first TWO stages of half h of the forward transform on one row's gadget digits, exactly, from the DECOMPOSED WORDS of the
 // coefficients: w0[r] / w1[r] hold the word of e = lane + 64 r and e + 512 with the sign mask applied, the row's digit is the signed field
@@ -72,9 +85,11 @@ __device__ __forceinline__ void ll_split_first_stages_words(double (&x)[kRegs8],
     }
 }
 
+template <bool TABLE>
 __global__ __launch_bounds__(kLlThreads) void blind_rotate_ll_kernel(
     const LinDesc* __restrict__ descs, int count, const double* __restrict__ bk_ntt,
-    const Ntt512Tables* __restrict__ gt2, int steps, uint32_t* __restrict__ acc_dump, const uint32_t* __restrict__ tvs)
+    const Ntt512Tables* __restrict__ gt2, int steps, uint32_t* __restrict__ acc_dump, const uint32_t* __restrict__ tvs,
+    const uint32_t* const* __restrict__ tables)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int g = blockIdx.x;
@@ -109,11 +124,21 @@ __global__ __launch_bounds__(kLlThreads) void blind_rotate_ll_kernel(
     __syncthreads();
     {   // RotatedTestVector, include/gatebootstrapping_gpu.cuh:29-52 (mu or the descriptor's user test vector)
         const uint32_t bbar = *bbar_slot;
-        const uint32_t* tv = desc_tv(tvs, d.pad);
-        for (int e = tid; e < kN; e += kLlThreads) {
-            const uint32_t v = rotated_tv_coef(tv, bbar, (uint32_t)e);
-            accL[e] = 0; accL[kN + e] = 0;
-            accL[2 * kN + e] = v; accL[3 * kN + e] = v;
+        const uint32_t* tab = nullptr;
+        if constexpr (TABLE) tab = tables[g];
+        if (TABLE && tab) {         // ... or X^bbar times both polynomials of the rotation's table
+            for (int e = tid; e < kN; e += kLlThreads) {
+                const uint32_t a = rotated_tv_coef(tab, bbar, (uint32_t)e), v = rotated_tv_coef(tab + kN, bbar, (uint32_t)e);
+                accL[e] = a; accL[kN + e] = a;
+                accL[2 * kN + e] = v; accL[3 * kN + e] = v;
+            }
+        } else {
+            const uint32_t* tv = desc_tv(tvs, d.pad);
+            for (int e = tid; e < kN; e += kLlThreads) {
+                const uint32_t v = rotated_tv_coef(tv, bbar, (uint32_t)e);
+                accL[e] = 0; accL[kN + e] = 0;
+                accL[2 * kN + e] = v; accL[3 * kN + e] = v;
+            }
         }
     }
     __syncthreads();
@@ -282,6 +307,8 @@ __global__ __launch_bounds__(kLlThreads) void blind_rotate_ll_kernel(
             for (int e = tid; e < kN; e += kLlThreads) extract_more(o, 1 << s, (uint32_t)e, accL[e], accL[2 * kN + e]);
     }
 }
+CUFHE_AMD_LL_INSTANCE(false)
+CUFHE_AMD_LL_INSTANCE(true)
 #endif
 
 // ----------------------------------------------------------------------------------
@@ -300,13 +327,25 @@ constexpr int kLl2LdsRot = kLlLdsTiles + 16 * kTile512Bytes;
 constexpr int kLl2LdsBytes = kLl2LdsRot + 2 * kLl2RotBytes + 16;                                  // 157008 (+ the inverse waves' counter)
 static_assert(kLl2LdsBytes <= 160 * 1024, "paired low-latency kernel does not fit the CU's LDS");
 
+template <bool TABLE>      // TABLE: as for blind_rotate_ll_kernel
 __global__ __launch_bounds__(kLlThreads) void blind_rotate_ll2_kernel(
     const LinDesc* __restrict__ descs, int count, const double* __restrict__ bk_ntt,
-    const Ntt512Tables* __restrict__ gt2, int steps, uint32_t* __restrict__ acc_dump, uint32_t* fault, const uint32_t* __restrict__ tvs);
+    const Ntt512Tables* __restrict__ gt2, int steps, uint32_t* __restrict__ acc_dump, uint32_t* fault, const uint32_t* __restrict__ tvs,
+    const uint32_t* const* __restrict__ tables);
+#define CUFHE_AMD_LL2_INSTANCE(T)                                                                                                 \
+    template __global__ void blind_rotate_ll2_kernel<T>(const LinDesc* __restrict__, int, const double* __restrict__,             \
+                                                        const Ntt512Tables* __restrict__, int, uint32_t* __restrict__, uint32_t*, \
+                                                        const uint32_t* __restrict__, const uint32_t* const* __restrict__);
+#ifdef CUFHE_AMD_LL_DECLARATIONS_ONLY
+extern CUFHE_AMD_LL2_INSTANCE(false)
+extern CUFHE_AMD_LL2_INSTANCE(true)
+#endif
 #ifndef CUFHE_AMD_LL_DECLARATIONS_ONLY
+template <bool TABLE>
 __global__ __launch_bounds__(kLlThreads) void blind_rotate_ll2_kernel(
     const LinDesc* __restrict__ descs, int count, const double* __restrict__ bk_ntt,
-    const Ntt512Tables* __restrict__ gt2, int steps, uint32_t* __restrict__ acc_dump, uint32_t* fault, const uint32_t* __restrict__ tvs)
+    const Ntt512Tables* __restrict__ gt2, int steps, uint32_t* __restrict__ acc_dump, uint32_t* fault, const uint32_t* __restrict__ tvs,
+    const uint32_t* const* __restrict__ tables)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
@@ -356,10 +395,19 @@ __global__ __launch_bounds__(kLlThreads) void blind_rotate_ll2_kernel(
 #pragma unroll
     for (int x = 0; x < 2; x++) {   // RotatedTestVector, include/gatebootstrapping_gpu.cuh:29-52 (mu or the descriptor's user test vector)
         const uint32_t bbar = *rot[x].bbar;
-        const uint32_t* tv = desc_tv(tvs, dsc[x].pad);
-        for (int e = tid; e < kN; e += kLlThreads) {
-            rot[x].acc[e] = 0;
-            rot[x].acc[kN + e] = rotated_tv_coef(tv, bbar, (uint32_t)e);
+        const uint32_t* tab = nullptr;
+        if constexpr (TABLE) tab = tables[gidx[x]];
+        if (TABLE && tab) {         // ... or X^bbar times both polynomials of the rotation's table
+            for (int e = tid; e < kN; e += kLlThreads) {
+                rot[x].acc[e] = rotated_tv_coef(tab, bbar, (uint32_t)e);
+                rot[x].acc[kN + e] = rotated_tv_coef(tab + kN, bbar, (uint32_t)e);
+            }
+        } else {
+            const uint32_t* tv = desc_tv(tvs, dsc[x].pad);
+            for (int e = tid; e < kN; e += kLlThreads) {
+                rot[x].acc[e] = 0;
+                rot[x].acc[kN + e] = rotated_tv_coef(tv, bbar, (uint32_t)e);
+            }
         }
     }
     __syncthreads();
@@ -564,6 +612,8 @@ __global__ __launch_bounds__(kLlThreads) void blind_rotate_ll2_kernel(
         }
     }
 }
+CUFHE_AMD_LL2_INSTANCE(false)
+CUFHE_AMD_LL2_INSTANCE(true)
 #endif
 
 // ----------------------------------------------------------------------------------

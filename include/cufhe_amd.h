@@ -507,6 +507,37 @@ int cufhe_amd_pack_initialize(const uint32_t* key, size_t words);
 int cufhe_amd_pack_batch(int device, void* stream, size_t count_in, const uint32_t* tlwe0, const int32_t* dst, const int32_t* pos,
                          size_t count_out, uint32_t* trlwe);
 
+/* ---- encrypted-table lookup: blind rotation from a caller's TRLWE (no counterpart in the reference) ----
+ * The blind rotation of the gates reads a PLAINTEXT table: its accumulator starts as (0, X^bbar TV).  Here it starts from a ciphertext:
+ * for a TRLWE T = (A, B) ([2][N], the a polynomial first), a lvl0 TLWE x and nout = 2^s outputs,
+ *     abar_i = ms_abar(x_i, s), bbar = ms_bbar(x_n, s)                      the roundings of section 9.1 (s = 0: the gates' own)
+ *     acc_0 = (X^bbar A, X^bbar B)                                          the negacyclic product of section 11 on both polynomials
+ *     acc_{i+1} = CMux(BK_i, X^abar_i acc_i, acc_i),  i < steps             the unchanged steps of the gates' rotation
+ *     LutRotate(T, x, s) = acc_steps;   LutLookup output j = KeySwitch(SampleExtract(j)(acc_n)),  0 <= j < nout
+ * so a table (0, TV) gives the words of a user gate defined on TV with coefficients (1, 0, 0) and offset 0 (nout > 1: of the
+ * multi-output definition), and a table built on the device -- gates, cufhe_amd_pack_batch, cufhe_amd_trlwe_spread_batch -- is read by an
+ * encrypted index in ONE rotation.  Every word is exact and independent of the launch shape.  tables[table_count][2][N], tlwe0 and the
+ * outputs are device arrays; src is a HOST array of count entries (staged through the stream's workspace like the exponents of section
+ * 11; NULL: src[g] = g), rotation g reads tables[src[g]] and several rotations may name one table.  Refused before any device work: -1
+ * for a null pointer (src excepted), nout not 1, 2, 4 or 8, src[g] outside [0, table_count), table_count = 0 with count > 0, an output
+ * array overlapping tables, or "param_set" active; -3 without cufhe_amd_initialize.  Default parameter set only; the N = 2048 ring and
+ * the parameter sets have none of this.  There is no recorded form (cufhe_amd_stream_fence orders a call behind the gates recorded on
+ * its stream), no linear combination of several address ciphertexts inside the call (a user gate forms the address) and no key
+ * generation. */
+/* acc[count][2][N]: LutRotate after `steps` CMux steps (outside [0, n]: all n, as in cufhe_amd_blind_rotate_batch) */
+int cufhe_amd_lut_rotate_batch(int device, void* stream, size_t count, const uint32_t* tlwe0, const uint32_t* tables, size_t table_count,
+                               const int32_t* src, int nout, int steps, uint32_t* acc);
+/* tlwe0_out[count][nout][n+1]: all nout outputs of every item, from one rotation launch sequence and one key-switch launch (the path of
+ * the multi-output gates at level 0) */
+int cufhe_amd_lut_lookup_batch(int device, void* stream, size_t count, const uint32_t* tlwe0, const uint32_t* tables, size_t table_count,
+                               const int32_t* src, int nout, uint32_t* tlwe0_out);
+/* Spread (no key, needs no cufhe_amd_initialize): out[g] = X^(-stride floor(reps/2)) sum_{i < reps} X^(i stride) in[g] on both
+ * polynomials of TRLWEs [count][2][N], mod 2^32, negacyclic.  It turns a packed TRLWE into a table whose entries fill boxes: values[m]
+ * at coefficient m N / p with stride = 1, reps = N / p gives, for a trivial (0, .), cufhe_amd_test_vector(values, p) word for word (the
+ * top half box holding -values[0] included); values[j][m] at m N / p + j with stride = nout, reps = N / (p nout) gives
+ * cufhe_amd_test_vector_multi.  -1: a null pointer, stride < 1, reps < 1, stride * reps > N, out overlapping in, "param_set" active. */
+int cufhe_amd_trlwe_spread_batch(int device, void* stream, size_t count, const uint32_t* in, int stride, int reps, uint32_t* out);
+
 /* ---- other parameter sets (CMakeLists.txt:8-24: USE_80BIT_SECURITY / USE_CGGI19 / USE_CONCRETE select TFHEpp
  * parameter headers at build time; k > 1: src/bootstrap_gpu.cu:402-421; N = 512: include/ntt_gpu/ntt_gpuntt.cuh:283-329)
  * Every set of cufhe_amd/csrc/kernels_ps.hip.h is compiled in and chosen by index: 0 = the default set (the same

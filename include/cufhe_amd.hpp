@@ -596,6 +596,53 @@ inline void gPackTLWEs(cuFHETRLWElvl1& out, const std::vector<Ctxt<TFHEpp::lvl0p
     (void)cufhe_amd_free(dev, gathered);
     CUFHE_AMD_CHECK(rc);
 }
+/// Encrypted-table lookup (include/cufhe_amd.h, cufhe_amd_lut_lookup_batch): the blind rotation of the
+/// gates with a CIPHERTEXT as its table -- a TRLWE built on the device by gates, gPackTLWEs and gSpreadTRLWE is read by an encrypted
+/// index in one rotation.  All three are device-buffer forms and, like gPackTLWEs, not recorded: the stream is fenced first, so a call
+/// runs behind the gates recorded on `st` and what is recorded afterwards runs behind it.  Default parameter set only.
+/// out = Spread(in): X^(-stride floor(reps/2)) sum_{i < reps} X^(i stride) in -- entries at coefficients m N / p fill their boxes
+/// with stride 1, reps N / p.  out must not be in.
+inline void gSpreadTRLWE(cuFHETRLWElvl1& out, const cuFHETRLWElvl1& in, int stride, int reps, Stream st)
+{
+    const int dev = st.device_id();
+    CUFHE_AMD_CHECK(cufhe_amd_stream_fence(dev, st.raw()));
+    CUFHE_AMD_CHECK(cufhe_amd_trlwe_spread_batch(dev, st.raw(), 1, cufhe_amd_ctxt_device_ptr(in.handle, dev), stride, reps,
+                                                 cufhe_amd_ctxt_device_ptr(out.handle, dev)));
+}
+/// out = the accumulator of the blind rotation of `table` by the lvl0 ciphertext `addr`, nout = 1, 2, 4 or 8 (the rounding of the
+/// multi-output gates).  out must not be table.
+inline void gBlindRotateTRLWE(cuFHETRLWElvl1& out, const cuFHETRLWElvl1& table, const Ctxt<TFHEpp::lvl0param>& addr, Stream st, int nout = 1)
+{
+    const int dev = st.device_id();
+    CUFHE_AMD_CHECK(cufhe_amd_stream_fence(dev, st.raw()));
+    CUFHE_AMD_CHECK(cufhe_amd_lut_rotate_batch(dev, st.raw(), 1, cufhe_amd_ctxt_device_ptr(addr.handle, dev),
+                                               cufhe_amd_ctxt_device_ptr(table.handle, dev), 1, nullptr, nout, -1,
+                                               cufhe_amd_ctxt_device_ptr(out.handle, dev)));
+}
+/// *outs[j] = output j of the lookup of `table` at the encrypted address `addr` (1, 2, 4 or 8 outputs: one rotation, one key-switch
+/// launch); the results are scattered to the outputs' device buffers by a Copy launch on the same stream.  Returns when they are there.
+inline void gLookupTRLWE(const std::vector<Ctxt<TFHEpp::lvl0param>*>& outs, const cuFHETRLWElvl1& table, const Ctxt<TFHEpp::lvl0param>& addr,
+                         Stream st)
+{
+    const int dev = st.device_id();
+    const size_t nout = outs.size(), words = (size_t)cufhe_amd_ctxt_words(0);
+    CUFHE_AMD_CHECK(cufhe_amd_stream_fence(dev, st.raw()));
+    void* res = nullptr;
+    CUFHE_AMD_CHECK(cufhe_amd_malloc(dev, (nout ? nout : 1) * words * sizeof(uint32_t), &res));
+    int rc = cufhe_amd_lut_lookup_batch(dev, st.raw(), 1, cufhe_amd_ctxt_device_ptr(addr.handle, dev),
+                                        cufhe_amd_ctxt_device_ptr(table.handle, dev), 1, nullptr, (int)nout, static_cast<uint32_t*>(res));
+    std::vector<int32_t> ops(nout, (int32_t)CUFHE_AMD_COPY);
+    std::vector<uint32_t*> dsts(nout);
+    std::vector<const uint32_t*> srcs(nout);
+    for (size_t j = 0; j < nout; j++) {
+        dsts[j] = cufhe_amd_ctxt_device_ptr(outs[j]->handle, dev);
+        srcs[j] = static_cast<const uint32_t*>(res) + j * words;
+    }
+    if (rc >= 0) rc = cufhe_amd_gate_list(dev, st.raw(), 0, nout, ops.data(), dsts.data(), srcs.data(), nullptr, nullptr);
+    if (rc >= 0) rc = cufhe_amd_stream_synchronize(dev, st.raw());
+    (void)cufhe_amd_free(dev, res);
+    CUFHE_AMD_CHECK(rc);
+}
 
 #undef CUFHE_AMD_GATE1
 #undef CUFHE_AMD_GATE2

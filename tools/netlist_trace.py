@@ -29,7 +29,7 @@ print(f"{len(seg)} chain steps over {(seg[-1][1] - t0) / 1e6:.1f} ms")
 print("chain step durations (ms):", " ".join(f"{(r[1] - r[0]) / 1e6:.2f}" for r in seg))
 print("chain step periods (start to start, ms):", " ".join(f"{(b[0] - a[0]) / 1e6:.2f}" for a, b in zip(seg, seg[1:])))
 inwin = [r for r in rows if r[0] >= t0 - 25_000_000 and r[1] <= seg[-1][1] + 40_000_000]
-bulk = [r for r in inwin if r[2].startswith("cufhe_amd::blind_rotate_kernel") or "blind_rotate_kernel(" in r[2]]
+bulk = [r for r in inwin if "cufhe_amd::blind_rotate_kernel" in r[2] or "blind_rotate_kernel(" in r[2]]
 print("batch-kernel launches in the window (start ms, duration ms, workgroups):")
 for r in bulk:
     print(f"  {(r[0] - t0) / 1e6:8.2f} {(r[1] - r[0]) / 1e6:7.2f} {r[3] // max(1, r[4])}")
