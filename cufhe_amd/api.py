@@ -545,6 +545,48 @@ def lvl2_keyswitch_batch(tlwe2, tlwe0, count, device=0, stream=None):
     check(lib.cufhe_amd_lvl2_keyswitch_batch(device, stream, count, tlwe2.ptr, tlwe0.ptr))
 
 
+# ---- user gates on the N = 2048 ring (cufhe_amd_lvl2_define_gate, include/cufhe_amd.h) ----
+LVL2_USER_OP_BASE, LVL2_MAX_USER_GATES, LVL2_N = 8192, 64, 2048
+
+
+def lvl2_define_gate(coeffs, offset=0, test_vector=None):
+    """A user gate of the N = 2048 ring: x = c0 in0 + c1 in1 + c2 in2 + (0, .., 0, offset) on lvl0 ciphertexts, bootstrapped through
+    `test_vector` (2048 uint64 torus words; None: the constant 2^61).  Returns the op id: an op of lvl2_gate_batch, and of gate_batch /
+    Apply / gApply at level 0 while "lvl0_ring" is 2048."""
+    c = np.zeros(3, dtype=np.int32)
+    c[:len(coeffs)] = coeffs
+    tv = None
+    if test_vector is not None:
+        tv = np.ascontiguousarray(test_vector, dtype=np.uint64)
+        if tv.size != LVL2_N:
+            raise ValueError(f"test vector must have N2 = {LVL2_N} words")
+    op = ctypes.c_int()
+    check(lib.cufhe_amd_lvl2_define_gate(c.ctypes.data_as(_lib.c_i32p), int(offset) & 0xFFFFFFFF, _ptr(tv) if tv is not None else None,
+                                         ctypes.byref(op)))
+    return op.value
+
+
+def lvl2_test_vector(values):
+    """The 64-bit test vector of a function on len(values) messages (a power of two, 2 .. N2/2) encoded with a padding bit at level 0,
+    m -> m 2^32 / (2p): values are the output torus words, uint64 (cufhe_amd_lvl2_test_vector)."""
+    v = np.ascontiguousarray(values, dtype=np.uint64)
+    tv = np.empty(LVL2_N, dtype=np.uint64)
+    check(lib.cufhe_amd_lvl2_test_vector(_ptr(v), int(v.size), _ptr(tv)))
+    return tv
+
+
+def lvl2_user_rotate_batch(op, in0, acc, count, in1=None, in2=None, steps=-1, device=0, stream=None):
+    """acc[count][2][N2] (uint64): the accumulator of lvl2 user gate `op` after `steps` CMux steps (parity hook)."""
+    check(lib.cufhe_amd_lvl2_user_rotate_batch(device, stream, count, op, in0.ptr, in1.ptr if in1 is not None else None,
+                                               in2.ptr if in2 is not None else None, steps, acc.ptr))
+
+
+def lvl2_user_extract_batch(op, in0, tlwe2, count, in1=None, in2=None, device=0, stream=None):
+    """tlwe2[count][N2 + 1] (uint64): lvl2 user gate `op` without its key switch -- the input form of private_keyswitch_batch."""
+    check(lib.cufhe_amd_lvl2_user_extract_batch(device, stream, count, op, in0.ptr, in1.ptr if in1 is not None else None,
+                                                in2.ptr if in2 is not None else None, tlwe2.ptr))
+
+
 # ---- circuit bootstrapping: lvl0 TLWE -> lvl1 TRGSW (include/cufhe_amd.h) ----
 def cb_params():
     p = CbParams()

@@ -88,6 +88,7 @@ struct DeviceState {
     double* bk2q_ntt = nullptr;        // the same key in the quarter layout
     bool br2q_lds_opt_in = false;
     uint32_t* ksk2 = nullptr;
+    uint64_t* tvs2 = nullptr;          // [kMaxUserGates2][k2N]: the lvl2 user gates' test vectors (cufhe_amd_lvl2_define_gate); CleanUp frees it
     uint32_t* cb_pksk = nullptr;       // circuit bootstrapping: the private key-switching key lvl2 -> lvl1 (cb.inc.h)
     uint32_t* pack_key = nullptr;      // TLWE packing: the lvl0 -> TRLWE key-switching key (pack.inc.h)
     std::vector<EventPair> br_events, ks_events;
@@ -491,6 +492,30 @@ bool is_seiks_at(int op) { return op >= CUFHE_AMD_TL_SEIKS_AT(0) && op <= CUFHE_
 bool is_cmux_rotate(int op) { return op >= CUFHE_AMD_TL_CMUX_ROTATE(0) && op <= CUFHE_AMD_TL_CMUX_ROTATE(2 * kN - 1); }
 int fail_packed_rom_set() { return fail(-1, "packed ROM words (TRLWE rotation, rotating CMUX, indexed SampleExtract) run on the default path only: not with \"param_set\" active"); }
 
+// User gates of the N = 2048 ring (cufhe_amd_lvl2_define_gate, lvl2.inc.h): definitions of their own in an id range of their own,
+// single output, 64-bit test vectors in row k of every device's DeviceState::tvs2.  Same write-once discipline as g_user.
+static_assert(CUFHE_AMD_LVL2_MAX_USER_GATES == kMaxUserGates2, "the header's capacity is the device table's");
+static_assert(CUFHE_AMD_LVL2_USER_OP_BASE > CUFHE_AMD_TL_CMUX_ROTATE(2 * kN - 1) && CUFHE_AMD_LVL2_USER_OP_BASE > CUFHE_AMD_TL_SEIKS_AT(kN - 1) &&
+                  CUFHE_AMD_LVL2_USER_OP_BASE >= CUFHE_AMD_USER_OP_BASE + (kMaxUserGates << kMaxOutputShift) &&
+                  CUFHE_AMD_LVL2_USER_OP_BASE > CUFHE_AMD_TL_CIRCUIT_BOOTSTRAP && CUFHE_AMD_LVL2_USER_OP_BASE >= CUFHE_AMD_NUM_OPS,
+              "lvl2 user op ids lie above every other id range");
+UserGate g_user2[kMaxUserGates2];
+std::atomic<int> g_user2_count{0};
+bool is_lvl2_user_op(int op) { return op >= CUFHE_AMD_LVL2_USER_OP_BASE && op < CUFHE_AMD_LVL2_USER_OP_BASE + kMaxUserGates2; }
+// the definition of `op`; nullptr when op is not a defined lvl2 user gate
+const UserGate* lvl2_user_gate(int op)
+{
+    if (!is_lvl2_user_op(op)) return nullptr;
+    const int k = op - CUFHE_AMD_LVL2_USER_OP_BASE;
+    return k < g_user2_count.load(std::memory_order_acquire) ? &g_user2[k] : nullptr;
+}
+int fail_lvl2_user_op() { return fail(-1, "lvl2 user gate op not defined (cufhe_amd_lvl2_define_gate; CleanUp drops the definitions)"); }
+int fail_lvl2_user_path()
+{
+    return fail(-1, "lvl2 user gates run on the N = 2048 ring only: lvl0 ciphertexts through cufhe_amd_lvl2_gate_batch or with \"lvl0_ring\" 2048, "
+                    "not with \"param_set\" active");
+}
+
 int user_def(int op) { return (op - CUFHE_AMD_USER_OP_BASE) % kMaxUserGates; }      // definition index k of a user op id
 int user_output(int op) { return (op - CUFHE_AMD_USER_OP_BASE) / kMaxUserGates; }   // output j of a user op id
 // the definition of `op`; nullptr when op is not a defined user gate or names an output j >= nout of one
@@ -539,6 +564,9 @@ long g_param_set = -1;
 //   lvl1_gates         whether it has gates on Mid ciphertexts (level 1)
 //   s, ready(), rotate(), keyswitch()   its device, the readiness check and the two launchers
 //   user_gates         whether its rotation kernels read LinDesc::pad as a test-vector row (user gates; the default path only)
+//   lvl2_user_gates    whether it runs the lvl2 user gates (RotDesc2::pad = kPadRow2 + row; the N = 2048 ring only); then rotate() takes
+//                      one more argument: whether any descriptor names a row
+//   user_op(op), tv_pad(op, u)   the path's own definition lookup (nullptr: not a defined user gate of this path) and pad rule
 // Level 0: blind rotate -> key switch (__HomGate__ br -> iks); level 1: key switch -> blind rotate (iks -> br); Not / Copy and the
 // level-1 Mux sums run last, as one lincomb.  The three-input user gates' c0 in0 + c1 in1 run first, as one lincomb into temporaries.
 template <class P, class GetGate>
@@ -550,10 +578,22 @@ int lower_gates(const P& p, hipStream_t st, int level, size_t count, GetGate get
             if (is_user_op(get(g).op))
                 return fail(-1, "user gates run on the default path only: not with \"param_set\" active or on the N = 2048 ring (\"lvl0_ring\")");
     }
+    if constexpr (!P::lvl2_user_gates) {
+        for (size_t g = 0; g < count; g++)
+            if (is_lvl2_user_op(get(g).op)) return fail_lvl2_user_path();
+    } else {
+        for (size_t g = 0; g < count; g++) {
+            const int op = get(g).op;
+            if (!is_lvl2_user_op(op)) continue;
+            if (g_param_set >= 0 || level != 0) return fail_lvl2_user_path();
+            if (!lvl2_user_gate(op)) return fail_lvl2_user_op();
+        }
+    }
     if (int rc = p.ready()) return rc;
     if (level != 0 && level != 1) return fail(-1, "level must be 0 or 1");
     if (count == 0) return 0;
     const uint32_t negmu = 0u - kMu;
+    bool tv_rows = false;         // a rotation descriptor names a test-vector row (read by the lvl2 path's launcher only)
 
     // Outputs of one multi-output definition on the same operands form one evaluation (one rotation, all nout outputs extracted into
     // scratch): fused by (definition, in0, in1, in2) whatever the order of the list.  fuse[g] is the evaluation of gate g.
@@ -587,6 +627,13 @@ int lower_gates(const P& p, hipStream_t st, int level, size_t count, GetGate get
             nrot += 1;
             if (user_gate_arity(*u) == 3) npre += 1;
             continue;
+        }
+        if constexpr (P::lvl2_user_gates) {
+            if (const UserGate* u = P::user_op(op)) {
+                nrot += 1;
+                if (user_gate_arity(*u) == 3) npre += 1;
+                continue;
+            }
         }
         if (op < 0 || op >= CUFHE_AMD_NUM_OPS) return fail(-1, "unknown gate op");
         if (op == CUFHE_AMD_MUX || op == CUFHE_AMD_NMUX) nrot += 2;
@@ -659,7 +706,9 @@ int lower_gates(const P& p, hipStream_t st, int level, size_t count, GetGate get
                 else lin.push_back({(const uint32_t*)tj, (const uint32_t*)tj, (uint32_t*)gr.out, 1, 0, 0u, 0u});
                 continue;
             }
-            if (const UserGate* u = user_gate(gr.op)) {
+        }
+        if constexpr (P::user_gates || P::lvl2_user_gates) {
+            if (const UserGate* u = P::user_op(gr.op)) {
                 // x = c0 in0 + c1 in1 + c2 in2 + (0, ..., 0, off) through the two-input gate path; the rotation starts from the
                 // definition's test vector (LinDesc::pad = row + 1) or from mu (pad 0)
                 const int arity = user_gate_arity(*u);
@@ -673,12 +722,13 @@ int lower_gates(const P& p, hipStream_t st, int level, size_t count, GetGate get
                     pre.push_back({gr.in0, gr.in1, t, u->c[0], u->c[1], 0u, 0u});
                     a = t; b = gr.in2; ca = 1; cb = u->c[2];
                 }
-                const uint32_t pad = u->tv ? (uint32_t)(gr.op - CUFHE_AMD_USER_OP_BASE) + 1 : 0u;
+                const uint32_t pad = P::tv_pad(gr.op, *u);
+                tv_rows |= pad != 0;
                 if (level == 0) {
                     Mid* t1 = tmp1 + ir * P::mid_words;
                     rot.push_back({a, b, t1, ca, cb, u->off, pad});
                     ks.push_back({t1, t1, gr.out, 1, 0, 0u});
-                } else {
+                } else if constexpr (P::lvl1_gates) {
                     uint32_t* t0 = tmp0 + ir * P::lvl0_words;
                     ks.push_back({a, b, t0, ca, cb, u->off});
                     rot.push_back({t0, t0, gr.out, 1, 0, 0u, pad});
@@ -737,9 +787,13 @@ int lower_gates(const P& p, hipStream_t st, int level, size_t count, GetGate get
     if (int rc = upload_descs(p.s, sc, pre, &dpre)) return rc;
     if (int rc = launch_lincomb(st, dpre, pre.size(), (int)level_words)) return rc;
     if (level == 0) {
-        if (int rc = p.rotate(st, drot, rot.size(), P::n, nullptr)) return rc;
+        if constexpr (P::lvl2_user_gates) {
+            if (int rc = p.rotate(st, drot, rot.size(), P::n, nullptr, tv_rows)) return rc;
+        } else {
+            if (int rc = p.rotate(st, drot, rot.size(), P::n, nullptr)) return rc;
+        }
         if (int rc = p.keyswitch(st, dks, ks.size())) return rc;
-    } else {
+    } else if constexpr (P::lvl1_gates) {
         if (int rc = p.keyswitch(st, dks, ks.size())) return rc;
         if (int rc = p.rotate(st, drot, rot.size(), P::n, nullptr)) return rc;
     }
@@ -883,7 +937,9 @@ struct BasePath {
     using Mid = uint32_t;
     static constexpr int lvl0_words = kLvl0Words, mid_words = kLvl1Words, n = kLvl0N;
     static constexpr uint32_t ks_mu = kMu;
-    static constexpr bool lvl1_gates = true, has_cmux = true, user_gates = true, packed_rom = true;
+    static constexpr bool lvl1_gates = true, has_cmux = true, user_gates = true, packed_rom = true, lvl2_user_gates = false;
+    static const UserGate* user_op(int op) { return user_gate(op); }
+    static uint32_t tv_pad(int op, const UserGate& u) { return u.tv ? (uint32_t)(op - CUFHE_AMD_USER_OP_BASE) + 1 : 0u; }
     static constexpr size_t trlwe_words = 2 * kN;
     static constexpr auto se_kernel = sample_extract_desc_kernel;
     DeviceState& s;
@@ -913,6 +969,13 @@ int run_gates(int device, void* stream, int level, size_t count, GetGate get)
         if (!is_user_op(op)) continue;
         if (!user_gate(op)) return fail_user_op(op);
         if (!user_ok) return fail(-1, "user gates run on the default path only: not with \"param_set\" active or on the N = 2048 ring (\"lvl0_ring\")");
+    }
+    // lvl2 user ops: only where the gates run through the N = 2048 ring
+    for (size_t g = 0; g < count; g++) {
+        const int op = get(g).op;
+        if (!is_lvl2_user_op(op)) continue;
+        if (g_param_set >= 0 || level != 0 || g_lvl0_ring != 2048) return fail_lvl2_user_path();
+        if (!lvl2_user_gate(op)) return fail_lvl2_user_op();
     }
     if (level == 0 && g_lvl0_ring == 2048) return run_gates_lvl2(device, stream, count, get);
     if ((level == 0 || level == 1) && g_param_set >= 0) return run_gates_ps((int)g_param_set, device, stream, level, count, get);
@@ -1145,6 +1208,7 @@ int cufhe_amd_cleanup(void)
         }
         if (s.keys_ready) { HIP_TRY(hipFree(s.bk_ntt)); HIP_TRY(hipFree(s.ksk)); }
         if (s.tvs) { HIP_TRY(hipFree(s.tvs)); s.tvs = nullptr; }
+        if (s.tvs2) { HIP_TRY(hipFree(s.tvs2)); s.tvs2 = nullptr; }
         ps_release(i);
         if (s.keys2_ready) { if (s.bk2_ntt) HIP_TRY(hipFree(s.bk2_ntt)); HIP_TRY(hipFree(s.bk2q_ntt)); HIP_TRY(hipFree(s.ksk2)); }
         if (s.cb_pksk) { HIP_TRY(hipFree(s.cb_pksk)); s.cb_pksk = nullptr; }
@@ -1166,6 +1230,7 @@ int cufhe_amd_cleanup(void)
     }
     lvl2_release_host_key();
     g_user_count.store(0, std::memory_order_release);
+    g_user2_count.store(0, std::memory_order_release);
     return 0;
 }
 

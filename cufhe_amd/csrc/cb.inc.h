@@ -38,7 +38,7 @@ int cb_rotate(DeviceState& s, hipStream_t st, Scratch& sc, size_t count, const u
             h[g * kCbL + r] = RotDesc2{tlwe0 + g * kLvl0Words, tlwe0 + g * kLvl0Words, tlwe2 + (g * kCbL + r) * kPksIn, 1, 0, 0u, cb_mu_log2(r)};
     RotDesc2* d;
     if (int rc = upload_descs(s, sc, h, &d)) return rc;
-    if (int rc = launch_blind_rotate_lvl2(s, st, d, h.size(), kLvl0N, nullptr)) return rc;
+    if (int rc = launch_blind_rotate_lvl2(s, st, d, h.size(), kLvl0N, nullptr, false)) return rc;
     const int n = (int)h.size();
     hipLaunchKernelGGL(cb_add_mu_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, tlwe2, n);
     HIP_TRY(hipGetLastError());
@@ -96,7 +96,7 @@ int lower_cb_ops(DeviceState& s, hipStream_t st, const GateRef* g, size_t n)
         for (int r = 0; r < kCbL; r++) h[c * kCbL + r] = RotDesc2{ins[c], ins[c], t2 + (c * kCbL + r) * kPksIn, 1, 0, 0u, cb_mu_log2(r)};
     RotDesc2* d;
     if (int rc = upload_descs(s, sc, h, &d)) return rc;
-    if (int rc = launch_blind_rotate_lvl2(s, st, d, h.size(), kLvl0N, nullptr)) return rc;
+    if (int rc = launch_blind_rotate_lvl2(s, st, d, h.size(), kLvl0N, nullptr, false)) return rc;
     hipLaunchKernelGGL(cb_add_mu_kernel, dim3((unsigned)((h.size() + 255) / 256)), dim3(256), 0, st, t2, (int)h.size());
     HIP_TRY(hipGetLastError());
     if (int rc = launch_private_keyswitch(s, st, t2, count * kCbL, tg, kCbL)) return rc;

@@ -69,9 +69,28 @@ struct RotDesc2 {          // lvl0 operands, lvl2 result (sample-extracted TLWE)
     uint64_t* out;
     int32_t ca, cb;
     uint32_t off;
-    uint32_t pad;          // test vector: 0 = the constant k2Mu, else the constant 2^pad (circuit bootstrapping: desc_mu2)
+    uint32_t pad;          // test vector: 0 = the constant k2Mu, 1..63 = the constant 2^pad (circuit bootstrapping: desc_mu2),
+                           // kPadRow2 + row = row `row` of the lvl2 user gates' table (cufhe_amd_lvl2_define_gate)
 };
 __host__ __device__ constexpr uint64_t desc_mu2(uint32_t pad) { return pad ? 1ull << (pad & 63) : k2Mu; }
+// lvl2 user gates: the rotation starts from (0, X^bbar TV), TV a row of tvs[kMaxUserGates2][k2N].  Only the <true> instantiations of
+// the two rotation kernels read the table; a launch whose descriptors name no row runs <false>, the kernels as they were.
+constexpr int kMaxUserGates2 = 64;
+constexpr uint32_t kPadRow2 = 64;
+static_assert(kPadRow2 > 63, "rows lie above every constant pad");
+__host__ __device__ constexpr bool desc_has_row2(uint32_t pad) { return pad >= kPadRow2; }
+// coefficient e of X^bbar TV in Z[X]/(X^2048 + 1), 1 <= bbar <= 2 N: TV[(e - bbar) mod N], negated where the exponent wraps an odd
+// number of times; bbar = 2 N is the identity
+__device__ __forceinline__ uint64_t rotated_tv_coef2(const uint64_t* __restrict__ tv, uint32_t bbar, uint32_t e)
+{
+    const uint32_t k = (e - bbar) & (2 * k2N - 1);
+    const uint64_t v = tv[k & (k2N - 1)];
+    return k >= (uint32_t)k2N ? 0ull - v : v;
+}
+__device__ __forceinline__ const uint64_t* desc_tv2(const uint64_t* __restrict__ tvs, uint32_t pad)
+{
+    return tvs + (size_t)((pad - kPadRow2) & (kMaxUserGates2 - 1)) * k2N;
+}
 struct LinDesc64 {         // out(lvl0) = KS(ca * in0 + cb * in1 + (0, .., off)) on lvl2 TLWEs
     const uint64_t* in0;
     const uint64_t* in1;
@@ -247,9 +266,10 @@ constexpr int k3LdsBytes = k3LdsTu + 2 * 256;                    // 153872
 static_assert(k3LdsBytes <= 160 * 1024, "lvl2 blind rotate does not fit the CU's LDS");
 static_assert(2 * k2Half * 8 <= 2 * k2Half * 8 && 2 * k2N * 8 <= 2 * 2 * k2Half * 8, "accumulator copy fits two sum polynomials per component");
 
+template <bool TV>
 __global__ __launch_bounds__(k2Threads) void blind_rotate_lvl2_kernel(
     const RotDesc2* __restrict__ descs, int count, const double* __restrict__ bk_ntt,
-    const NttTables* __restrict__ gt2, int steps, uint64_t* __restrict__ acc_dump)
+    const NttTables* __restrict__ gt2, int steps, uint64_t* __restrict__ acc_dump, const uint64_t* __restrict__ tvs)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int g = blockIdx.x;
@@ -293,6 +313,16 @@ __global__ __launch_bounds__(k2Threads) void blind_rotate_lvl2_kernel(
             const bool n1 = (bbar != 2 * k2N) && ((e1 < (bbar & (k2N - 1))) != ((bbar >> k2Nbit) != 0));
             acc_lo[m] = wj ? (n0 ? 0ull - mu : mu) : 0ull;
             acc_hi[m] = wj ? (n1 ? 0ull - mu : mu) : 0ull;
+        }
+        if constexpr (TV) {
+            if (desc_has_row2(d.pad) && wj) {      // a user gate: this wave's 8 words of X^bbar TV, gathered once (uniform per workgroup and wave)
+                const uint64_t* tv = desc_tv2(tvs, d.pad);
+#pragma unroll
+                for (int m = 0; m < 4; m++) {
+                    acc_lo[m] = rotated_tv_coef2(tv, bbar, (uint32_t)(e_first + 64 * m));
+                    acc_hi[m] = rotated_tv_coef2(tv, bbar, (uint32_t)(e_first + 64 * m + k2Half));
+                }
+            }
         }
     }
     // the LDS copy of acc_j for the rotated reads: sum polynomials (h, o) = (j, 3 j) and (j, 3 j + 1) -- of those the slice

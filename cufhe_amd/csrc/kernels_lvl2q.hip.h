@@ -323,9 +323,12 @@ __global__ __launch_bounds__(kNttThreads) void bk2q_to_ntt_kernel(
 // ----------------------------------------------------------------------------------
 // Blind rotate lvl02 + sample extract: one 4-wave workgroup per rotation, two workgroups per CU.
 // ----------------------------------------------------------------------------------
+// TV (both rotation kernels of this ring): the instantiation that also reads the lvl2 user gates' table `tvs` for descriptors whose pad
+// names a row (kernels_lvl2.hip.h: kPadRow2); <false> is the kernel as it was and serves every launch without such a descriptor.
+template <bool TV>
 __global__ __launch_bounds__(kQThreads, 2) void blind_rotate_lvl2q_kernel(
     const RotDesc2* __restrict__ descs, int count, const double* __restrict__ bk_ntt,
-    const Ntt512Tables* __restrict__ tq, int steps, uint64_t* __restrict__ acc_dump)
+    const Ntt512Tables* __restrict__ tq, int steps, uint64_t* __restrict__ acc_dump, const uint64_t* __restrict__ tvs)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int g = blockIdx.x;
@@ -386,6 +389,15 @@ __global__ __launch_bounds__(kQThreads, 2) void blind_rotate_lvl2q_kernel(
                 acc[0][s][t] = 0ull;
                 acc[1][s][t] = neg ? 0ull - mu : mu;
             }
+        if constexpr (TV) {
+            if (desc_has_row2(d.pad)) {      // a user gate: this lane's 8 words of X^bbar TV, gathered once (uniform per workgroup)
+                const uint64_t* tv = desc_tv2(tvs, d.pad);
+#pragma unroll
+                for (int s = 0; s < 2; s++)
+#pragma unroll
+                    for (int t = 0; t < 4; t++) acc[1][s][t] = rotated_tv_coef2(tv, bbar, (uint32_t)(e_base + 64 * s + kQPoints * t));
+            }
+        }
     }
     char* own = smem + opaque(kQLdsR + 8 * e_base);        // + 16384 j + 512 s + 4096 t: this lane's words in the copy / its exchange slots
     auto publish_acc = [&]() {

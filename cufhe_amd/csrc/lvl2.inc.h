@@ -62,7 +62,9 @@ void lvl2_release_host_key()
     std::vector<uint64_t>().swap(g_bk2_host);
 }
 
-int launch_blind_rotate_lvl2(DeviceState& s, hipStream_t st, const RotDesc2* d, size_t count, int steps, uint64_t* acc_dump)
+// tv_rows: a descriptor names a row of the lvl2 user gates' table (pad >= kPadRow2): the launch runs the <true> instantiation, which
+// also handles constant pads; every other launch (built-in gates, circuit bootstrapping) runs <false>, the kernels as they were
+int launch_blind_rotate_lvl2(DeviceState& s, hipStream_t st, const RotDesc2* d, size_t count, int steps, uint64_t* acc_dump, bool tv_rows)
 {
     if (count == 0) return 0;
     ProfScope prof{s, st, count, false};
@@ -70,19 +72,21 @@ int launch_blind_rotate_lvl2(DeviceState& s, hipStream_t st, const RotDesc2* d, 
     if (plan::lvl2_quarters(count, cus_of(s), g_tuning)) {
         // four quarter waves per rotation, two rotations per CU (kernels_lvl2q.hip.h)
         if (!s.br2q_lds_opt_in) {
-            HIP_TRY(hipFuncSetAttribute((const void*)blind_rotate_lvl2q_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kQLdsBytes));
+            HIP_TRY(hipFuncSetAttribute((const void*)blind_rotate_lvl2q_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, kQLdsBytes));
+            HIP_TRY(hipFuncSetAttribute((const void*)blind_rotate_lvl2q_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, kQLdsBytes));
             s.br2q_lds_opt_in = true;
         }
-        hipLaunchKernelGGL(blind_rotate_lvl2q_kernel, dim3((unsigned)count), dim3(kQThreads), kQLdsBytes, st, d, (int)count,
-                           s.bk2q_ntt, s.tables2q, steps, acc_dump);
+        hipLaunchKernelGGL(tv_rows ? blind_rotate_lvl2q_kernel<true> : blind_rotate_lvl2q_kernel<false>, dim3((unsigned)count), dim3(kQThreads),
+                           kQLdsBytes, st, d, (int)count, s.bk2q_ntt, s.tables2q, steps, acc_dump, s.tvs2);
     } else {
         if (int rc = ensure_bk2_half_layout(s)) return rc;
         if (!s.br2_lds_opt_in) {
-            HIP_TRY(hipFuncSetAttribute((const void*)blind_rotate_lvl2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, k3LdsBytes));
+            HIP_TRY(hipFuncSetAttribute((const void*)blind_rotate_lvl2_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, k3LdsBytes));
+            HIP_TRY(hipFuncSetAttribute((const void*)blind_rotate_lvl2_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, k3LdsBytes));
             s.br2_lds_opt_in = true;
         }
-        hipLaunchKernelGGL(blind_rotate_lvl2_kernel, dim3((unsigned)count), dim3(k2Threads), k3LdsBytes, st, d, (int)count,
-                           s.bk2_ntt, s.tables2, steps, acc_dump);
+        hipLaunchKernelGGL(tv_rows ? blind_rotate_lvl2_kernel<true> : blind_rotate_lvl2_kernel<false>, dim3((unsigned)count), dim3(k2Threads),
+                           k3LdsBytes, st, d, (int)count, s.bk2_ntt, s.tables2, steps, acc_dump, s.tvs2);
     }
     HIP_TRY(hipGetLastError());
     return prof.commit();
@@ -110,10 +114,13 @@ struct Lvl2Path {
     using Mid = uint64_t;
     static constexpr int lvl0_words = kLvl0Words, mid_words = k2Words, n = kLvl0N;
     static constexpr uint64_t ks_mu = k2Mu;
-    static constexpr bool lvl1_gates = false, user_gates = false;
+    static constexpr bool lvl1_gates = false, user_gates = false, lvl2_user_gates = true;
+    // the ring's own definitions (cufhe_amd_lvl2_define_gate): an op of cufhe_amd_define_gate stays refused here
+    static const UserGate* user_op(int op) { return lvl2_user_gate(op); }
+    static uint32_t tv_pad(int op, const UserGate& u) { return u.tv ? kPadRow2 + (uint32_t)(op - CUFHE_AMD_LVL2_USER_OP_BASE) : 0u; }
     DeviceState& s;
     int ready() const { return s.keys2_ready ? 0 : fail(-3, "cufhe_amd_lvl2_initialize has not been called for this device"); }
-    int rotate(hipStream_t st, const RotDesc2* d, size_t count, int steps, uint64_t* dump) const { return launch_blind_rotate_lvl2(s, st, d, count, steps, dump); }
+    int rotate(hipStream_t st, const RotDesc2* d, size_t count, int steps, uint64_t* dump, bool tv_rows) const { return launch_blind_rotate_lvl2(s, st, d, count, steps, dump, tv_rows); }
     int keyswitch(hipStream_t st, const LinDesc64* d, size_t count) const { return launch_keyswitch_lvl2(s, st, d, count); }
 };
 
@@ -122,6 +129,52 @@ int run_gates_lvl2(int device, void* stream, size_t count, GetGate get)
 {
     if (int rc = use_device(device)) return rc;
     return lower_gates(Lvl2Path{g_dev[device]}, (hipStream_t)stream, 0, count, get);
+}
+
+// The parity hooks of the lvl2 user gates: `count` evaluations of definition `op` on [count][n + 1] arrays, with the rotation
+// descriptors of the gate path (lower_gates: arity, the pre-added c0 in0 + c1 in1 of three operands, the pad) and another tail: the
+// accumulator after `steps` steps (acc), or the sample-extracted lvl2 TLWE without its key switch (tlwe2).
+int lvl2_user_rotations(int device, void* stream, size_t count, int op, const uint32_t* in0, const uint32_t* in1, const uint32_t* in2,
+                        int steps, uint64_t* acc, uint64_t* tlwe2)
+{
+    if (int rc = use_device(device)) return rc;
+    DeviceState& s = g_dev[device];
+    if (!is_lvl2_user_op(op)) return fail(-1, "op is not in the lvl2 user gates' id range (CUFHE_AMD_LVL2_USER_OP_BASE + k)");
+    if (g_param_set >= 0) return fail_lvl2_user_path();
+    const UserGate* u = lvl2_user_gate(op);
+    if (!u) return fail_lvl2_user_op();
+    if (!s.keys2_ready) return fail(-3, "cufhe_amd_lvl2_initialize has not been called for this device");
+    if (!in0 || (!acc && !tlwe2)) return fail(-1, "null pointer");
+    const int arity = user_gate_arity(*u);
+    if (arity >= 2 && !in1) return fail(-1, "user gate needs a second operand");
+    if (arity == 3 && !in2) return fail(-1, "user gate needs a third operand");
+    if (count == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    Scratch sc;
+    if (int rc = open_scratch(s, st, count * (sizeof(RotDesc2) + sizeof(LinDesc) + (arity == 3 ? kLvl0Words * sizeof(uint32_t) : 0)) + 4096, &sc)) return rc;
+    uint32_t* tmpp = nullptr;
+    if (arity == 3)
+        if (int rc = sc.alloc((void**)&tmpp, count * kLvl0Words * sizeof(uint32_t))) return rc;
+    const uint32_t pad = Lvl2Path::tv_pad(op, *u);
+    std::vector<RotDesc2> rot(count);
+    std::vector<LinDesc> pre;
+    for (size_t g = 0; g < count; g++) {
+        const uint32_t* a = in0 + g * kLvl0Words;
+        const uint32_t* b = arity >= 2 ? in1 + g * kLvl0Words : a;
+        int32_t ca = u->c[0], cb = u->c[1];
+        if (arity == 3) {
+            uint32_t* t = tmpp + g * kLvl0Words;
+            pre.push_back({a, b, t, u->c[0], u->c[1], 0u, 0u});
+            a = t; b = in2 + g * kLvl0Words; ca = 1; cb = u->c[2];
+        }
+        rot[g] = RotDesc2{a, b, tlwe2 ? tlwe2 + g * k2Words : nullptr, ca, cb, u->off, pad};
+    }
+    RotDesc2* drot;
+    LinDesc* dpre;
+    if (int rc = upload_descs(s, sc, rot, &drot)) return rc;
+    if (int rc = upload_descs(s, sc, pre, &dpre)) return rc;
+    if (int rc = launch_lincomb(st, dpre, pre.size(), kLvl0Words)) return rc;
+    return launch_blind_rotate_lvl2(s, st, drot, count, steps, acc, pad != 0);
 }
 
 }  // namespace
@@ -198,6 +251,66 @@ int cufhe_amd_lvl2_gate_batch(int device, void* stream, size_t count, const int3
     });
 }
 
+int cufhe_amd_lvl2_define_gate(const int32_t coeffs[3], uint32_t offset, const uint64_t* test_vector, int* op)
+{
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (!coeffs || !op) return fail(-1, "null pointer");
+    if (coeffs[0] == 0) return fail(-1, "lvl2 user gate: c0 must not be 0");
+    if (g_param_set >= 0) return fail(-1, "lvl2 user gates run on the N = 2048 ring only: not while \"param_set\" is active");
+    for (int i = 0; i < g_gpu_num; i++)
+        if (!g_dev[i].keys2_ready) return fail(-3, "cufhe_amd_lvl2_initialize has not been called for every device");
+    const int k = g_user2_count.load(std::memory_order_relaxed);
+    if (k >= kMaxUserGates2) return fail(-1, "lvl2 user gate table full (CUFHE_AMD_LVL2_MAX_USER_GATES definitions until CleanUp)");
+    // build first, swap last: the tables of the devices that have none yet are all allocated before any is installed; row k of every
+    // table is written synchronously, and no launch reads the row before its id exists
+    std::vector<DevPtr<uint64_t>> fresh((size_t)g_gpu_num);
+    for (int i = 0; i < g_gpu_num; i++) {
+        if (g_dev[i].tvs2) continue;
+        HIP_TRY(hipSetDevice(phys_device(i)));
+        HIP_TRY(fresh[(size_t)i].alloc((size_t)kMaxUserGates2 * k2N));
+    }
+    if (test_vector)
+        for (int i = 0; i < g_gpu_num; i++) {
+            uint64_t* t = g_dev[i].tvs2 ? g_dev[i].tvs2 : fresh[(size_t)i].p;
+            HIP_TRY(hipSetDevice(phys_device(i)));
+            HIP_TRY(hipMemcpy(t + (size_t)k * k2N, test_vector, k2N * sizeof(uint64_t), hipMemcpyHostToDevice));
+        }
+    for (int i = 0; i < g_gpu_num; i++)
+        if (!g_dev[i].tvs2) g_dev[i].tvs2 = fresh[(size_t)i].release();
+    g_user2[k] = UserGate{{coeffs[0], coeffs[1], coeffs[2]}, offset, test_vector != nullptr, 1, 0};
+    g_user2_count.store(k + 1, std::memory_order_release);
+    *op = CUFHE_AMD_LVL2_USER_OP_BASE + k;
+    return 0;
+}
+
+int cufhe_amd_lvl2_test_vector(const uint64_t* values, int p, uint64_t* tv)
+{
+    if (!values || !tv) return fail(-1, "null pointer");
+    if (p < 2 || p > k2N / 2 || (p & (p - 1))) return fail(-1, "p must be a power of two in [2, N2/2]");
+    // the boxes of cufhe_amd_test_vector on N2 coefficients: m = round(j p / N2), the top half-box (m = p) holds -values[0]
+    const int box = k2N / p;
+    for (int j = 0; j < k2N; j++) {
+        const int m = (j + box / 2) / box;
+        tv[j] = m == p ? 0ull - values[0] : values[m];
+    }
+    return 0;
+}
+
+int cufhe_amd_lvl2_user_rotate_batch(int device, void* stream, size_t count, int op, const uint32_t* in0, const uint32_t* in1,
+                                     const uint32_t* in2, int steps, uint64_t* acc)
+{
+    if (!acc) return fail(-1, "null pointer");
+    if (steps < 0 || steps > kLvl0N) steps = kLvl0N;
+    return lvl2_user_rotations(device, stream, count, op, in0, in1, in2, steps, acc, nullptr);
+}
+
+int cufhe_amd_lvl2_user_extract_batch(int device, void* stream, size_t count, int op, const uint32_t* in0, const uint32_t* in1,
+                                      const uint32_t* in2, uint64_t* tlwe2)
+{
+    if (!tlwe2) return fail(-1, "null pointer");
+    return lvl2_user_rotations(device, stream, count, op, in0, in1, in2, kLvl0N, nullptr, tlwe2);
+}
+
 int cufhe_amd_lvl2_blind_rotate_batch(int device, void* stream, size_t count, const uint32_t* tlwe0, uint64_t* acc, int steps)
 {
     if (int rc = use_device(device)) return rc;
@@ -207,7 +320,7 @@ int cufhe_amd_lvl2_blind_rotate_batch(int device, void* stream, size_t count, co
     if (steps < 0 || steps > kLvl0N) steps = kLvl0N;
     hipStream_t st = (hipStream_t)stream;
     return direct_batch(s, st, count, [&](size_t g) { return RotDesc2{tlwe0 + g * kLvl0Words, tlwe0 + g * kLvl0Words, nullptr, 1, 0, 0u, 0u}; },
-                        [&](const RotDesc2* d) { return launch_blind_rotate_lvl2(s, st, d, count, steps, acc); });
+                        [&](const RotDesc2* d) { return launch_blind_rotate_lvl2(s, st, d, count, steps, acc, false); });
 }
 
 int cufhe_amd_lvl2_keyswitch_batch(int device, void* stream, size_t count, const uint64_t* tlwe2, uint32_t* tlwe0)

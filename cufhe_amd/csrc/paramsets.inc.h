@@ -115,7 +115,7 @@ struct PsPath {
     using Mid = uint32_t;
     static constexpr int lvl0_words = D::lvl0_words, mid_words = D::lvl1_words, n = PS::n;
     static constexpr uint32_t ks_mu = kMu;
-    static constexpr bool lvl1_gates = true, has_cmux = !PS::small_modulus, user_gates = false, packed_rom = false;
+    static constexpr bool lvl1_gates = true, has_cmux = !PS::small_modulus, user_gates = false, packed_rom = false, lvl2_user_gates = false;
     static constexpr size_t trlwe_words = (size_t)D::K1 * D::N;
     static constexpr auto se_kernel = sample_extract_ps_kernel<PS>;
     DeviceState& s;

@@ -446,9 +446,16 @@ int cufhe_amd_enqueue_gate(int device, void* stream, int op, int copying, cufhe_
     if (int rc = check_device(device)) return rc;
     const UserGate* u = user_gate(op);     // a user gate: an ordinary gate of one, two or three operands, kind = its output level
     if (is_user_op(op) && !u) return fail_user_op(op);
+    // a lvl2 user gate (cufhe_amd_lvl2_define_gate): the same, for lvl0 ciphertexts while they bootstrap through the N = 2048 ring
+    const bool u2 = is_lvl2_user_op(op);
+    if (u2) {
+        if (!out || !in0) return fail(-1, "null ciphertext");
+        if (g_param_set >= 0 || g_lvl0_ring != 2048 || out->level != 0) return fail_lvl2_user_path();
+        if (!(u = lvl2_user_gate(op))) return fail_lvl2_user_op();
+    }
     if (!u && (op < 0 || op >= CUFHE_AMD_NUM_OPS)) return fail(-1, "unknown gate op");
     if (!out || !in0) return fail(-1, "null ciphertext");
-    if (u && (g_param_set >= 0 || (g_lvl0_ring == 2048 && out->level == 0)))
+    if (u && !u2 && (g_param_set >= 0 || (g_lvl0_ring == 2048 && out->level == 0)))
         return fail(-1, "user gates run on the default path only: not with \"param_set\" active or on the N = 2048 ring (\"lvl0_ring\")");
     const bool three = op == CUFHE_AMD_MUX || op == CUFHE_AMD_NMUX || (u && user_gate_arity(*u) == 3);
     const bool one = op == CUFHE_AMD_NOT || op == CUFHE_AMD_COPY || (u && user_gate_arity(*u) == 1);
@@ -474,6 +481,7 @@ int cufhe_amd_enqueue_gate_multi(int device, void* stream, int op, int copying, 
 {
     std::lock_guard<std::mutex> lk(g_sched_mu);
     if (int rc = check_device(device)) return rc;
+    if (is_lvl2_user_op(op)) return fail(-1, "enqueue_gate_multi: lvl2 user gates have one output (cufhe_amd_enqueue_gate)");
     const UserGate* u = user_gate(op);
     if (is_user_op(op) && !u) return fail_user_op(op);
     if (!u || user_output(op) != 0 || u->nout < 2) return fail(-1, "enqueue_gate_multi: op must be a multi-output user gate (cufhe_amd_define_gate_multi)");

@@ -132,8 +132,9 @@ int cufhe_amd_gate_list(int device, void* stream, int level, size_t count, const
  * range overlaps neither enum cufhe_amd_op nor enum cufhe_amd_trlwe_op.  Definitions are immutable; the test vector is copied into
  * every device's table before the call returns.  cufhe_amd_cleanup drops every definition: its id is refused afterwards.
  * Refused: c0 = 0 (-1); a full table (-1); a definition while "param_set" is active (-1); before cufhe_amd_initialize (-3).  The
- * parameter-set kernels ("param_set") and the N = 2048 ring ("lvl0_ring" 2048) have no user gates: a user op there returns -1 before
- * any device work, as does an op id in the range that is not defined. */
+ * parameter-set kernels ("param_set") have no user gates, and the N = 2048 ring ("lvl0_ring" 2048) has its own
+ * (cufhe_amd_lvl2_define_gate below): an op of this range there returns -1 before any device work, as does an op id in the range
+ * that is not defined. */
 #define CUFHE_AMD_USER_OP_BASE 1000
 #define CUFHE_AMD_MAX_USER_GATES 64
 int cufhe_amd_define_gate(const int32_t coeffs[3], uint32_t offset, const uint32_t* test_vector, int* op);
@@ -446,6 +447,46 @@ int cufhe_amd_lvl2_blind_rotate_batch(int device, void* stream, size_t count, co
 /* tlwe2[count][N+1] (uint64) -> tlwe0[count][n+1] */
 int cufhe_amd_lvl2_keyswitch_batch(int device, void* stream, size_t count, const uint64_t* tlwe2,
                                    uint32_t* tlwe0);
+
+/* ---- user gates on the N = 2048 ring: programmable bootstrapping with 64-bit test vectors ----
+ * The ring has definitions of its own in an op-id range of its own; an op of cufhe_amd_define_gate stays refused on this ring.
+ * A lvl2 user gate is defined after cufhe_amd_lvl2_initialize: integer coefficients (c0, c1, c2), c0 != 0, a 32-bit torus offset and an
+ * optional test vector TV of N2 = 2048 uint64 torus words (NULL: the constant 2^61).  With lvl0 ciphertexts in0, in1, in2 and
+ *     x = c0 in0 + c1 in1 + c2 in2 + (0, ..., 0, offset)   mod 2^32
+ * the gate is the ring's two-input gate path on x -- lvl02 blind rotation, SampleExtract(0), lvl20 key switch -- except that the
+ * accumulator starts as (0, X^bbar TV) instead of (0, X^bbar mu): bbar = 2 N2 - (b >> (32 - 1 - 11)) as for the built-in gates,
+ * coefficient e reads TV[(e - bbar) mod N2], negated where (e < bbar mod N2) xor (bbar >= N2); bbar = 2 N2 is the identity and negates
+ * nothing.  So (ca, cb, 0) and offset of a built-in two-input gate with TV NULL, or an all-2^61 TV, give that gate's words exactly.
+ * Operands as cufhe_amd_define_gate: in0 only when c1 = c2 = 0, in0 and in1 when c2 = 0, else all three (c0 in0 + c1 in1 is formed
+ * first, into a temporary).
+ * Op ids: CUFHE_AMD_LVL2_USER_OP_BASE + k for the k-th definition since the last cufhe_amd_cleanup, k < CUFHE_AMD_LVL2_MAX_USER_GATES.
+ * The range 8192 .. 8255 lies above every other id range (enum cufhe_amd_op, enum cufhe_amd_trlwe_op, the user gates 1000 .. 1511,
+ * CUFHE_AMD_TL_SEIKS_AT 2048 .. 3071, CUFHE_AMD_TL_CMUX_ROTATE 4096 .. 6143; capi.hip asserts it).  Definitions are immutable; the test
+ * vector is copied into every device's table ([64][2048] uint64, 1 MB, allocated with the first definition) before the call returns.
+ * cufhe_amd_cleanup drops every definition.  Refused: c0 = 0, a full table, a null op, "param_set" active (-1); before
+ * cufhe_amd_lvl2_initialize (-3).
+ * Accepted, mixed freely with built-in ops: cufhe_amd_lvl2_gate_batch; and with "lvl0_ring" 2048 at level 0: cufhe_amd_gate,
+ * _gate_batch, _gate_list, _enqueue_gate.  Refused with -1 before any device work: a lvl2 op on the default ring, at level 1 or with
+ * "param_set" active; an id of the range without a definition; cufhe_amd_enqueue_gate_multi with a lvl2 op.
+ * Not built: multi-output definitions (extraction at an index j inside both rotation kernels), a level-1 form (the ring has no lvl1
+ * gates), tables that are themselves ciphertexts (the ring has no counterpart of cufhe_amd_lut_lookup_batch), and the circuit bootstrap
+ * that takes all l TRGSW rows from one rotation. */
+#define CUFHE_AMD_LVL2_USER_OP_BASE 8192
+#define CUFHE_AMD_LVL2_MAX_USER_GATES 64
+int cufhe_amd_lvl2_define_gate(const int32_t coeffs[3], uint32_t offset, const uint64_t* test_vector, int* op);
+/* Host helper: the boxes of cufhe_amd_test_vector on N2 = 2048 coefficients with 64-bit values: coefficient j in
+ * [m N2/p - N2/(2p), m N2/p + N2/(2p)) holds values[m], the top half-box [N2 - N2/(2p), N2) holds -values[0].  p a power of two,
+ * 2 <= p <= N2/2; lvl0 messages encoded as m -> m 2^32 / (2p).  values: p words, tv: N2 words. */
+int cufhe_amd_lvl2_test_vector(const uint64_t* values, int p, uint64_t* tv);
+/* Parity hook: in0 / in1 / in2 [count][n+1] device arrays (in1 / in2 NULL where the definition's arity does not read them);
+ * acc[count][2][N2] (uint64) is the accumulator of definition `op` after `steps` CMux steps (outside [0, n]: all n, as
+ * cufhe_amd_lvl2_blind_rotate_batch). */
+int cufhe_amd_lvl2_user_rotate_batch(int device, void* stream, size_t count, int op, const uint32_t* in0, const uint32_t* in1,
+                                     const uint32_t* in2, int steps, uint64_t* acc);
+/* The gate without its key switch: tlwe2[count][N2+1] (uint64) = SampleExtract(0) of the full rotation.  This is the high-precision
+ * output (64-bit torus, l = 4, Bgbit = 9) and the input form of cufhe_amd_private_keyswitch_batch and cufhe_amd_lvl2_keyswitch_batch. */
+int cufhe_amd_lvl2_user_extract_batch(int device, void* stream, size_t count, int op, const uint32_t* in0, const uint32_t* in1,
+                                      const uint32_t* in2, uint64_t* tlwe2);
 
 /* ---- circuit bootstrapping (CGGI17 section 4, TFHEpp's CircuitBootstrapping): lvl0 TLWE -> lvl1 TRGSW ----
  * For each input c and r = 0 .. l-1:

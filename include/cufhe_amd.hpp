@@ -382,6 +382,21 @@ inline std::vector<uint32_t> TestVector(const std::vector<uint32_t>& values)
     CUFHE_AMD_CHECK(cufhe_amd_test_vector(values.data(), (int)values.size(), tv.data()));
     return tv;
 }
+/// A user gate of the N = 2048 ring (cufhe_amd_lvl2_define_gate): define after lvl2::Initialize; tv: N2 = 2048 uint64 torus words
+/// (nullptr: the constant 2^61).  Apply / gApply take the handle on lvl0 ciphertexts while "lvl0_ring" is 2048; single output only.
+inline UserGate DefineGateLvl2(const std::array<int32_t, 3>& coeffs, uint32_t offset, const uint64_t* tv = nullptr)
+{
+    UserGate g;
+    CUFHE_AMD_CHECK(cufhe_amd_lvl2_define_gate(coeffs.data(), offset, tv, &g.op));
+    return g;
+}
+/// the 64-bit test vector of a function on values.size() lvl0 messages (a power of two, 2 .. N2/2) with a padding bit
+inline std::vector<uint64_t> TestVectorLvl2(const std::vector<uint64_t>& values)
+{
+    std::vector<uint64_t> tv(2048);
+    CUFHE_AMD_CHECK(cufhe_amd_lvl2_test_vector(values.data(), (int)values.size(), tv.data()));
+    return tv;
+}
 /// Apply: inputs from tlwehost, result delivered to out.tlwehost (like And); gApply: device buffers only (like gAnd)
 template <class P> inline void Apply(UserGate g, Ctxt<P>& out, Ctxt<P>& in0, Stream st)
 { CUFHE_AMD_CHECK(cufhe_amd_enqueue_gate(st.device_id(), st.raw(), g.op, 1, out.handle, in0.handle, nullptr, nullptr)); }
