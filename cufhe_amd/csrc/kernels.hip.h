@@ -116,25 +116,27 @@ __device__ __forceinline__ void rotate_sub(uint32_t (&temp)[kRegs], const uint32
 // One product into its accumulator: wide or narrow by the compile-time bound of the spectrum register (ntt_r4.h); LAST:
 // the product that completes the sum reduces it on the way (fpf::mulmod_add: one operation more than a plain product,
 // three fewer than a separate reduction in front of the inverse transform)
-template <class SPEC, int R, bool LAST>
+template <class SPEC, int R, bool LAST, bool FIRST = false>
 __device__ __forceinline__ void product_into(double& acc, double x, double w)
 {
     constexpr bool wide = r4::needs_wide(SPEC::in().v[R]);
+    static_assert(!(LAST && FIRST), "a sum of one product has no first row apart from its last");
     if constexpr (LAST) acc = wide ? fpf::mulmod_add_wide(x, w, acc) : fpf::mulmod_add(x, w, acc);
+    else if constexpr (FIRST) acc = wide ? fpf::mulmod_wide(x, w) : fpf::mulmod(x, w);
     else acc += wide ? fpf::mulmod_wide(x, w) : fpf::mulmod(x, w);
 }
-template <class SPEC, bool LAST, int Q>
+template <class SPEC, bool LAST, bool FIRST, int Q>
 __device__ __forceinline__ void pointwise_piece(double (&A0)[kRegs], double (&A1)[kRegs], const double (&x)[kRegs], const double2& b)
 {
     if constexpr (Q < 8) {
-        product_into<SPEC, 2 * Q, LAST>(A0[2 * Q], x[2 * Q], b.x);
-        product_into<SPEC, 2 * Q + 1, LAST>(A0[2 * Q + 1], x[2 * Q + 1], b.y);
+        product_into<SPEC, 2 * Q, LAST, FIRST>(A0[2 * Q], x[2 * Q], b.x);
+        product_into<SPEC, 2 * Q + 1, LAST, FIRST>(A0[2 * Q + 1], x[2 * Q + 1], b.y);
     } else {
-        product_into<SPEC, 2 * (Q - 8), LAST>(A1[2 * (Q - 8)], x[2 * (Q - 8)], b.x);
-        product_into<SPEC, 2 * (Q - 8) + 1, LAST>(A1[2 * (Q - 8) + 1], x[2 * (Q - 8) + 1], b.y);
+        product_into<SPEC, 2 * (Q - 8), LAST, FIRST>(A1[2 * (Q - 8)], x[2 * (Q - 8)], b.x);
+        product_into<SPEC, 2 * (Q - 8) + 1, LAST, FIRST>(A1[2 * (Q - 8) + 1], x[2 * (Q - 8) + 1], b.y);
     }
 }
-template <class SPEC, bool LAST, int Q = 0>
+template <class SPEC, bool LAST, bool FIRST, int Q = 0>
 __device__ __forceinline__ void pointwise_pieces(double (&A0)[kRegs], double (&A1)[kRegs], const double (&x)[kRegs],
                                                  double2 (&b)[16], const char* row_lane)
 {
@@ -148,16 +150,22 @@ __device__ __forceinline__ void pointwise_pieces(double (&A0)[kRegs], double (&A
     if constexpr (Q < 16) {
         if constexpr (Q + D < 16) b[Q + D] = *(const double2*)(row_lane + (Q + D) * 1024);
         __builtin_amdgcn_sched_barrier(0x0006);
-        pointwise_piece<SPEC, LAST, Q>(A0, A1, x, b[Q]);
+        pointwise_piece<SPEC, LAST, FIRST, Q>(A0, A1, x, b[Q]);
         __builtin_amdgcn_sched_barrier(0x0006);
-        pointwise_pieces<SPEC, LAST, Q + 1>(A0, A1, x, b, row_lane);
+        pointwise_pieces<SPEC, LAST, FIRST, Q + 1>(A0, A1, x, b, row_lane);
     }
 }
-template <class SPEC, bool LAST>
+// FIRST: the first product of a sum is WRITTEN to it (A0, A1 need no zeroing, and no addition to zero): the same value, since a
+// product is an integer-valued double and 0.0 + v == v (a zero product is +0.0 either way: its r + l is (-l) + l or 0 + 0)
+template <class SPEC, bool LAST, bool FIRST = false>
 __device__ __forceinline__ void pointwise_accumulate(double (&A0)[kRegs], double (&A1)[kRegs],
                                                      const double (&x)[kRegs], const char* row_lane)
 {
 #if defined(CUFHE_AMD_DIAGNOSTIC_BUILD) && defined(CUFHE_AMD_ABL_NO_BK)
+    if constexpr (FIRST) {
+#pragma unroll
+        for (int r = 0; r < kRegs; r++) { A0[r] = 0.0; A1[r] = 0.0; }
+    }
 #pragma unroll
     for (int q = 0; q < 8; q++) {
         A0[2 * q] += fpf::mulmod_wide(x[2 * q], 1234567.0 + q);
@@ -172,7 +180,7 @@ __device__ __forceinline__ void pointwise_accumulate(double (&A0)[kRegs], double
     double2 b[16];
 #pragma unroll
     for (int q = 0; q < D; q++) b[q] = *(const double2*)(row_lane + q * 1024);
-    pointwise_pieces<SPEC, LAST>(A0, A1, x, b, row_lane);
+    pointwise_pieces<SPEC, LAST, FIRST>(A0, A1, x, b, row_lane);
 }
 
 // The workgroup's row pipeline.  Row R (0 .. 6*steps-1) of the bootstrapping key is the
@@ -201,22 +209,30 @@ __device__ __forceinline__ void pointwise_accumulate(double (&A0)[kRegs], double
 #define CUFHE_AMD_ROW_SYNC(R) pipe.sync(R);
 #endif
 struct RowPipe {
-    const char* bk;          // NTT-domain key, bytes
+    // All of a request's address but `voff` is wave-uniform and lives in SGPRs: the global source is `src` (advanced by one row per
+    // request) + voff, the buffers are taken in turn by a wrapping byte offset -- no per-lane 64-bit address arithmetic, no R % 3.
+    const char* src;         // NTT-domain key, bytes: this wave's first piece of the next row to request
     char* buf;               // LDS: kBkRowBuffers x kBkRowBytes
+    uint32_t voff;           // lane * 16
     int wave, lane, total_rows;
     bool late;
-    __device__ __forceinline__ void issue(int R) const
+    int row_off;             // byte offset in buf of the buffer of the row last synchronised: (R % kBkRowBuffers) * kBkRowBytes
+    __device__ __forceinline__ RowPipe(const char* bk, char* buf_, int wave_, int lane_, int total_rows_, bool late_)
+        : src(bk + 2 * wave_ * 1024), buf(buf_), voff(lane_ * 16), wave(wave_), lane(lane_), total_rows(total_rows_), late(late_),
+          row_off((kBkRowBuffers - 1) * kBkRowBytes) {}
+    static __device__ __forceinline__ int next_off(int off) { return off == (kBkRowBuffers - 1) * kBkRowBytes ? 0 : off + kBkRowBytes; }
+    // requests row R, which must be the row behind the one last synchronised (or row 0 before the first sync)
+    __device__ __forceinline__ void issue(int R)
     {
-        if (R >= total_rows) return;
-        const char* src = bk + (size_t)R * kBkRowBytes + lane * 16;
-        char* dst = buf + (R % kBkRowBuffers) * kBkRowBytes;
+        if (R < total_rows) {
+            char* dst = buf + next_off(row_off) + 2 * wave * 1024;
 #pragma unroll
-        for (int c = 0; c < 2; c++) {
-            const int piece = 2 * wave + c;
-            lds_dma16(src + piece * 1024, dst + piece * 1024);
+            for (int c = 0; c < 2; c++) lds_dma16(src + c * 1024, voff, dst + c * 1024);
         }
+        src += kBkRowBytes;
     }
-    __device__ __forceinline__ void sync(int R) const
+    // rows are synchronised in order, R = 0, 1, 2, ..: once each by every wave
+    __device__ __forceinline__ void sync(int R)
     {
 #if defined(CUFHE_AMD_DIAGNOSTIC_BUILD) && defined(CUFHE_AMD_ABL_NO_SYNC)
         (void)R;             // timing only: no row barrier, no key traffic -- what the waves do when nothing couples them
@@ -224,12 +240,11 @@ struct RowPipe {
 #endif
         lds_dma_wait_all();  // this wave's pieces of row R (issued a row ago) have landed
         __syncthreads();     // s_waitcnt lgkmcnt(0); s_barrier
+        row_off = next_off(row_off);
         issue(R + 1);
     }
-    __device__ __forceinline__ const char* row(int R) const
-    {
-        return buf + opaque((R % kBkRowBuffers) * kBkRowBytes + lane * 16);
-    }
+    // the lane's 16 bytes of piece 0 of the row last synchronised
+    __device__ __forceinline__ const char* row() const { return buf + opaque(row_off + lane * 16); }
 };
 
 // The schedule of the step (ntt_r4.h): spectrum of a digit polynomial, the (k+1) l products per accumulator the last of
@@ -240,32 +255,46 @@ using BrInverse = r4::Inverse<BrSums>;
 static_assert(r4::valid(BrSpectrum::in()) && r4::valid(BrSums::in()) && r4::valid(BrInverse::Out::in()),
               "blind_rotate_kernel: the lazy-reduction schedule of the CMux step exceeds the FP64 mantissa");
 
+// one digit d of a component: its forward NTT, the row barrier, its product with TRGSW row `row` into both sums.  FIRST: the
+// row starts the sums (they hold nothing before); LAST: it completes them.
+template <bool FIRST, bool LAST>
+__device__ __forceinline__ void cmux_row(double (&A0)[kRegs], double (&A1)[kRegs], const uint32_t (&temp)[kRegs], int d,
+                                         const WaveCtx& ctx, RowPipe& pipe, int row, const TuFwdPinned& tuf CUFHE_AMD_DIAG_ARG)
+{
+    constexpr int kDigitMax = 1 << (kBgbit - 1);
+    const uint32_t pos = 32 - (d + 1) * kBgbit;  // v_bfe_i32: the sign-extended Bgbit-wide field at pos
+    double x[kRegs];
+#pragma unroll
+    for (int r = 0; r < kRegs; r++)
+        x[r] = (double)(int32_t)__builtin_amdgcn_sbfe(temp[r], pos, (uint32_t)kBgbit);
+    double twb[kTbCount];
+    ntt_forward_digits_a_r4<kDigitMax, true>(x, ctx, &tuf, &twb);
+    if (pipe.late) CUFHE_AMD_ROW_SYNC(row)
+    ntt_forward_digits_bc_r4<kDigitMax, false, true>(x, ctx, twb);
+    if (!pipe.late) CUFHE_AMD_ROW_SYNC(row)
+    pointwise_accumulate<BrSpectrum, LAST, FIRST>(A0, A1, x, pipe.row());
+}
+
 // one component j: rotate/subtract/decompose, then l forward NTTs, each multiplied into
-// both accumulators (include/gatebootstrapping_gpu.cuh:153-224).  LAST_COMPONENT: its last row completes both sums.
-template <bool LAST_COMPONENT>
+// both accumulators (include/gatebootstrapping_gpu.cuh:153-224).  FIRST_COMPONENT: its first row starts both sums;
+// LAST_COMPONENT: its last row completes them.  Those two rows stand outside the loop over the digits: chosen by a test of d
+// inside it, the forms of the product leave the sums in different registers and every pass copies all 32 back (64 v_mov_b64 per
+// step).  The loop itself stays rolled: unrolled, the step is 64 KB of code and the compiler spills
+// (profiles/r16_first_row_scalar_dma.md).
+template <bool FIRST_COMPONENT, bool LAST_COMPONENT>
 __device__ __forceinline__ void cmux_component(double (&A0)[kRegs], double (&A1)[kRegs],
                                                const uint32_t (&accj)[kRegs], const WaveCtx& ctx,
                                                char* tile, int lane, uint32_t abar,
-                                               const RowPipe& pipe, int first_row, const TuFwdPinned& tuf CUFHE_AMD_DIAG_ARG)
+                                               RowPipe& pipe, int first_row, const TuFwdPinned& tuf CUFHE_AMD_DIAG_ARG)
 {
-    constexpr int kDigitMax = 1 << (kBgbit - 1);
     uint32_t temp[kRegs];
     rotate_sub(temp, accj, tile, lane, abar);
+    static_assert(kL >= 2, "the first and the last row of a component are two rows");
+    constexpr int lo = FIRST_COMPONENT ? 1 : 0, hi = LAST_COMPONENT ? kL - 1 : kL;
+    if constexpr (FIRST_COMPONENT) cmux_row<true, false>(A0, A1, temp, 0, ctx, pipe, first_row, tuf CUFHE_AMD_DIAG_PASS);
 #pragma unroll 1
-    for (int d = 0; d < kL; d++) {
-        const uint32_t pos = 32 - (d + 1) * kBgbit;  // v_bfe_i32: the sign-extended Bgbit-wide field at pos
-        double x[kRegs];
-#pragma unroll
-        for (int r = 0; r < kRegs; r++)
-            x[r] = (double)(int32_t)__builtin_amdgcn_sbfe(temp[r], pos, (uint32_t)kBgbit);
-        double twb[kTbCount];
-        ntt_forward_digits_a_r4<kDigitMax, true>(x, ctx, &tuf, &twb);
-        if (pipe.late) CUFHE_AMD_ROW_SYNC(first_row + d)
-        ntt_forward_digits_bc_r4<kDigitMax, false, true>(x, ctx, twb);
-        if (!pipe.late) CUFHE_AMD_ROW_SYNC(first_row + d)
-        if (LAST_COMPONENT && d == kL - 1) pointwise_accumulate<BrSpectrum, true>(A0, A1, x, pipe.row(first_row + d));
-        else pointwise_accumulate<BrSpectrum, false>(A0, A1, x, pipe.row(first_row + d));
-    }
+    for (int d = lo; d < hi; d++) cmux_row<false, false>(A0, A1, temp, d, ctx, pipe, first_row + d, tuf CUFHE_AMD_DIAG_PASS);
+    if constexpr (LAST_COMPONENT) cmux_row<false, true>(A0, A1, temp, kL - 1, ctx, pipe, first_row + kL - 1, tuf CUFHE_AMD_DIAG_PASS);
 }
 
 template <bool TWB_LOADED>
@@ -302,7 +331,7 @@ __global__ __launch_bounds__(kBrThreads, 2) void blind_rotate_kernel(
     char* tile = smem + kBrLdsTiles + wave * kTileBytes;
     uint16_t* abar_lds = (uint16_t*)(smem + kBrLdsAbar + wave * kAbarBytes);
     const WaveCtx ctx = make_wave_ctx_packed(smem, kBrLdsTiles + wave * kTileBytes, kBrLdsTables, gt, lane);
-    const RowPipe pipe{(const char*)bk_ntt, smem + kBrLdsBk, wave, lane, steps * kBkRows, wave >= kBrWavesPerBlock / 2};
+    RowPipe pipe((const char*)bk_ntt, smem + kBrLdsBk, wave, lane, steps * kBkRows, wave >= kBrWavesPerBlock / 2);
     pipe.issue(0);
     if (wave >= active || g >= count) {
         // no rotation for this wave (tail of the batch): it only keeps its share of the row
@@ -374,11 +403,9 @@ __global__ __launch_bounds__(kBrThreads, 2) void blind_rotate_kernel(
         // abar = 0 needs no special case: all digits are zero and the step adds nothing
         const uint32_t abar = __builtin_amdgcn_readfirstlane((uint32_t)abar_lds[i]);
         double A0[kRegs], A1[kRegs], inv_twc[kTcCount], inv_twb[kTbCount];
-#pragma unroll
-        for (int r = 0; r < kRegs; r++) { A0[r] = 0.0; A1[r] = 0.0; }
-        // six products per accumulator, the last one reducing the sum (BrSums)
-        cmux_component<false>(A0, A1, acc0, ctx, tile, lane, abar, pipe, i * kBkRows, tuf CUFHE_AMD_DIAG_PASS);
-        cmux_component<true>(A0, A1, acc1, ctx, tile, lane, abar, pipe, i * kBkRows + kL, tuf CUFHE_AMD_DIAG_PASS);
+        // six products per accumulator, the first one starting the sum and the last one reducing it (BrSums)
+        cmux_component<true, false>(A0, A1, acc0, ctx, tile, lane, abar, pipe, i * kBkRows, tuf CUFHE_AMD_DIAG_PASS);
+        cmux_component<false, true>(A0, A1, acc1, ctx, tile, lane, abar, pipe, i * kBkRows + kL, tuf CUFHE_AMD_DIAG_PASS);
         // the two inverse transforms share their per-lane twiddles: fetched once
         load_packed(inv_twc, ctx.tc_inv);
         inverse_and_add<false>(A0, acc0, ctx, inv_twc, inv_twb);     // fetches the stage 7-4 twiddles ...

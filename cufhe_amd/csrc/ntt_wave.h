@@ -162,6 +162,17 @@ __device__ __forceinline__ void lds_dma16(const void* src, char* dst_uniform)
     asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(base) : "memory", "m0");
 #pragma clang diagnostic pop
 }
+// The same piece from `src_uniform + voff`: the source as a wave-uniform base in an SGPR pair plus a 32-bit per-lane byte
+// offset (the saddr + voffset form of the instruction), for callers whose lanes differ only in a term that never changes
+// (16 * lane): advancing the source is then scalar arithmetic, where the form above needs a 64-bit vector addition per request.
+__device__ __forceinline__ void lds_dma16(const char* src_uniform, uint32_t voff, char* dst_uniform)
+{
+    const uint32_t base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)dst_uniform;
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"
+    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(src_uniform), "s"(base) : "memory", "m0");
+#pragma clang diagnostic pop
+}
 __device__ __forceinline__ void lds_dma_wait_all() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 // A byte offset the compiler cannot see through: `lds + opaque(off)` keeps the full per-lane
@@ -262,17 +273,20 @@ __device__ __forceinline__ void ct_bfly_exact(double& a, double& b, double w)
 }
 
 // Stages 0 and 1 of a polynomial of small integers (gadget digits) as one exact radix-4 butterfly, see ct_four_stages<SMALL_IN>
-__device__ __forceinline__ void ct_exact_first_two(double (&x)[kRegs])
+// root4, root8: I and zeta as the caller holds them.  As literals they can only be the multiplier of the two-operand
+// v_fmac_f64, which overwrites its addend: each of the three addends that is used twice (a, a', u) is then copied first, 12
+// v_mov_b64 per transform.  From a scalar register pair (TuFwdPinned) they go into the three-operand v_fma_f64 and nothing is copied.
+__device__ __forceinline__ void ct_exact_first_two(double (&x)[kRegs], const double root4 = fpf::ROOT4, const double root8 = fpf::ROOT8)
 {
     constexpr double kZ3 = fpf::ROOT8 * fpf::ROOT8 * fpf::ROOT8;          // zeta^3 = 160 989 184 000, exact
 #pragma unroll
     for (int r = 0; r < 4; r++) {
         const double a = x[r], a1 = x[r + 4], b = x[r + 8], b1 = x[r + 12];
-        const double u = __builtin_fma(b, fpf::ROOT4, a), v = __builtin_fma(-b, fpf::ROOT4, a);
-        const double u1 = __builtin_fma(b1, fpf::ROOT4, a1);
+        const double u = __builtin_fma(b, root4, a), v = __builtin_fma(-b, root4, a);
+        const double u1 = __builtin_fma(b1, root4, a1);
         const double t = __builtin_fma(a1, kZ3, b1 * fpf::ROOT8);
-        x[r] = __builtin_fma(u1, fpf::ROOT8, u);
-        x[r + 4] = __builtin_fma(-u1, fpf::ROOT8, u);
+        x[r] = __builtin_fma(u1, root8, u);
+        x[r + 4] = __builtin_fma(-u1, root8, u);
         x[r + 8] = v + t;
         x[r + 12] = v - t;
     }
@@ -646,6 +660,7 @@ __device__ __forceinline__ void ntt_inverse(double (&x)[kRegs], const WaveCtx& c
 // the wave's LDS queue -- with the tile stores of STORE below in flight that wait sits in the middle of the pass.
 struct TuFwdPinned {
     double t[12];
+    double root4, root8;      // I and zeta for ct_exact_first_two, pinned the same way
     __device__ __forceinline__ void load(const NttTables* gt)
     {
 #pragma unroll
@@ -654,6 +669,9 @@ struct TuFwdPinned {
             asm volatile("" : "+s"(v));       // opaque: kept in an SGPR pair, never re-loaded
             t[k] = v;
         }
+        root4 = fpf::ROOT4;
+        root8 = fpf::ROOT8;
+        asm volatile("" : "+s"(root4), "+s"(root8));
     }
     __device__ __forceinline__ double operator()(int k) const { return t[k - 3]; }
 };
@@ -661,11 +679,12 @@ template <int DIGIT_MAX, bool STORE = false, class TW = TwUniform>
 __device__ __forceinline__ void ntt_forward_digits_a_r4(double (&x)[kRegs], const WaveCtx& c, const TW* pinned = nullptr, double (*twb_ahead)[kTbCount] = nullptr)
 {
     using A0 = typename r4::FwdDigits<DIGIT_MAX>::A0;
-    ct_exact_first_two(x);
-    if (!STORE) {
+    if constexpr (!STORE) {
+        ct_exact_first_two(x);
         r4::ct_pass_lo<A0, 3, 7>(x, TwUniform{c.gt->tu_fwd});
     } else {
         const TW& tw = *pinned;
+        ct_exact_first_two(x, tw.root4, tw.root8);
         if (twb_ahead) load_packed(*twb_ahead, c.tb_fwd);      // the stage 4-7 twiddles of ntt_forward_digits_bc_r4, requested a pass ahead of their use
         asm volatile("" ::: "memory");
         r4::Group<A0, false, 0>::ct(x, tw(3), tw(7), tw(8));

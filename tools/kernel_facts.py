@@ -7,6 +7,9 @@ clocks and launch times always come from the bench run itself.
 
 Usage (after the PMC passes of tools/profile_round.sh -- separate runs, --pmc with --kernel-trace only):
     python tools/kernel_facts.py --tag r03 --label "..." gpurun_out/r03_prof
+--only KEY (repeatable): the passes cover only these kernels (a change to one kernel, profiled with the workload that runs it); the
+other entries of the existing kernel_facts.json are kept as they are.  Only for a change after which the other kernels compile to
+the instructions they had -- compare the compiler's assembly first.
 Every argument is a directory (searched recursively) or a *_counter_collection.csv file.  Corrections applied as
 MI355X_MICROARCH.md (HBM) prescribes: FETCH_SIZE is in KB and counts half of a wide coalesced streaming read on gfx950
 (x2); WRITE_SIZE is exact; GRBM_GUI_ACTIVE is the sum over the 8 XCDs.
@@ -67,6 +70,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tag", default="r03")
     ap.add_argument("--label", default="")
+    ap.add_argument("--only", action="append", default=[], choices=sorted(KERNELS), help="replace only these entries, keep the others")
     ap.add_argument("paths", nargs="+")
     args = ap.parse_args()
     files = []
@@ -149,6 +153,13 @@ def main():
                 k_out["lds_pipe_busy"] = k_out["SQ_LDS_IDX_ACTIVE"] / (256 * clock * dur_ns * 1e-9)
         out["kernels"][k] = k_out
     dst = os.path.join(ROOT, "profiles", "kernel_facts.json")
+    if args.only:
+        missing = [k for k in args.only if k not in out["kernels"]]
+        if missing:
+            sys.exit(f"no rows of {missing} in the passes")
+        old = json.load(open(dst))
+        out["sources"] = sorted(set(old.get("sources", [])) | set(out["sources"]))
+        out["kernels"] = {k: (out["kernels"][k] if k in args.only else old["kernels"][k]) for k in old["kernels"]}
     json.dump(out, open(dst, "w"), indent=1)
     for f in files:      # keep the raw passes beside it, named per round and per pass
         shutil.copy(f, os.path.join(ROOT, "profiles", f"{args.tag}_{os.path.basename(os.path.dirname(f))}_counter_collection.csv"))
