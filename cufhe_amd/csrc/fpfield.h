@@ -52,6 +52,9 @@ constexpr double PINV = 0x1.491cc17c934a8p-50;    // fl(1/p)
 constexpr double ROOT4 = 29593600.0;              // I = zeta^2 = psi^512
 constexpr double ROOT8 = 5440.0;                  // zeta = psi^256
 constexpr double INV_ROOT4 = 0x1.22436485a6c7fp-25;   // fl(1/I)
+constexpr double ROOT8_CUBED = 160989184000.0;        // zeta^3 = psi^768
+constexpr double INV_ROOT8 = 0x1.8181818181818p-13;   // fl(1/zeta)
+constexpr double INV_ROOT8_CUBED = 0x1.b51a30f9739f8p-38;   // fl(1/zeta^3)
 constexpr double MAGIC0 = 6755399441055744.0;     // 1.5 * 2^52: adding it rounds to an integer
 constexpr double MAGIC1 = 13510798882111488.0;    // 1.5 * 2^53: rounds to an even integer
 
@@ -105,6 +108,25 @@ FPF_HD double mul_root4(double x)
     const double x0 = __builtin_fma(-x1, ROOT4, x);                    // exact: small integer
     return __builtin_fma(x0, ROOT4, -x1);                              // exact: |x0 I| < 2^48.7
 }
+// zeta*x mod p for any |x| < 2^53, zeta the eighth root of unity: p = zeta^4 + 1, so with x = x1 zeta^3 + x0 (x1 the nearest
+// integer to x / zeta^3, |x1| < 2^15.9; |x0| <= zeta^3/2 + 1: the quotient is taken from x fl(1/zeta^3), off by less than 2^-37)
+// zeta x = x1 zeta^4 + x0 zeta = x0 zeta - x1 -- the four operations of mul_root4, and the result is reduced:
+// |result| <= zeta^4/2 + zeta + 2^15.9 < (0.5 + 1e-10) p.
+FPF_HD double mul_root8(double x)
+{
+    const double x1 = __builtin_fma(x, INV_ROOT8_CUBED, MAGIC0) - MAGIC0;    // nearest integer to x / zeta^3
+    const double x0 = __builtin_fma(-x1, ROOT8_CUBED, x);                    // exact: an integer below 2^36.3
+    return __builtin_fma(x0, ROOT8, -x1);                                    // exact: |x0 zeta| < 2^48.7
+}
+// zeta^3*x mod p for any |x| < 2^53: with x = x1 zeta + x0 (x1 the nearest integer to x / zeta, |x1| < 2^40.6; |x0| <= zeta/2 + 1)
+// zeta^3 x = x1 zeta^4 + x0 zeta^3 = x0 zeta^3 - x1.  The quotient is large here and stays in the result:
+// |result| <= (zeta/2 + 1) zeta^3 + 2^53 / zeta = p/2 + zeta^3 + 2^40.6 < 0.50208 p.
+FPF_HD double mul_root8_cubed(double x)
+{
+    const double x1 = __builtin_fma(x, INV_ROOT8, MAGIC0) - MAGIC0;          // nearest integer to x / zeta
+    const double x0 = __builtin_fma(-x1, ROOT8, x);                          // exact: |x0| <= 2721
+    return __builtin_fma(x0, ROOT8_CUBED, -x1);                              // exact: |x0 zeta^3| < 2^48.7
+}
 // centred residue of any |a| < 2^53: |result| <= p/2 (+1 at a tie)
 FPF_HD double reduce(double a)
 {
@@ -131,7 +153,10 @@ FPF_HD uint32_t lift_u32_small(double a)
     __builtin_memcpy(&tb, &t, 8);
     return low32(a) - (uint32_t)tb * (uint32_t)P_U64;
 }
-
+// Torus word of a lazy residue that IS its true value: a = c + k p with |a| <= b p and |c| <= cmax forces k = 0 as soon as
+// b + cmax / p < 1 (lift_reduced_ok; the caller asserts it with the bound of its sums) -- the outputs of the root products
+// above are that small.  One FP64 operation, no reduction and no integer multiply.
+FPF_HD uint32_t lift_u32_reduced(double a) { return low32(a); }
 
 // ---- compile-time bounds (units of p), used by static_asserts where parameters enter ----
 constexpr double GROW = 0.09723;                 // p / 2^53, rounded up
@@ -143,5 +168,9 @@ constexpr double GROW_ADD = 0.14585;             // 1.5 p / 2^53, rounded up (mu
 constexpr double after_mulmod_add(double a) { return 0.5 + GROW_ADD * a; }        // |mulmod_add(a, w, c)|
 constexpr double after_mulmod_add_wide(double a) { return 1.0 + GROW_ADD * a; }   // |mulmod_add_wide(a, w, c)|
 constexpr double AFTER_MUL_ROOT4 = 0.5000005;    // |mul_root4(x)|
+constexpr double AFTER_MUL_ROOT8 = 0.5000001;    // |mul_root8(x)|: (zeta + 2^15.9) / p = 7e-11 above one half
+constexpr double AFTER_MUL_ROOT8_CUBED = 0.5021; // |mul_root8_cubed(x)|: (zeta^3 + 2^53 / zeta) / p = 0.002075 above one half
+// lift_u32_reduced: a register bounded by b (units of p) holds its true value when that is at most cmax (same units)
+constexpr bool lift_reduced_ok(double b, double cmax) { return b + cmax < 1.0; }
 
 }  // namespace fpf

@@ -251,9 +251,13 @@ struct RowPipe {
 // which reduces the sum, the inverse transform of that
 using BrSpectrum = r4::FwdDigits<(1 << (kBgbit - 1))>::Spectrum;
 using BrSums = r4::PointwiseSum<BrSpectrum, kBkRows, true>;
-using BrInverse = r4::Inverse<BrSums>;
+// the inverse with the root products in its last pass and the reductions its sums need, register by register (ntt_r4.h: InverseRootTail)
+using BrInverse = r4::InverseRootTail6x32<BrSums>;
 static_assert(r4::valid(BrSpectrum::in()) && r4::valid(BrSums::in()) && r4::valid(BrInverse::Out::in()),
               "blind_rotate_kernel: the lazy-reduction schedule of the CMux step exceeds the FP64 mantissa");
+// what the inverse returns is the sum itself, (k+1) l N (Bg/2) 2^31 at most: in thousandths of p, rounded up
+constexpr int kBrTrueMaxMilli = (int)(kExtProdSumBound / fpf::P * 1000.0) + 1;
+static_assert(kBrTrueMaxMilli < 500, "the sums of the CMux step must stay below p/2");
 
 // one digit d of a component: its forward NTT, the row barrier, its product with TRGSW row `row` into both sums.  FIRST: the
 // row starts the sums (they hold nothing before); LAST: it completes them.
@@ -301,8 +305,8 @@ template <bool TWB_LOADED>
 __device__ __forceinline__ void inverse_and_add(double (&A)[kRegs], uint32_t (&accj)[kRegs], const WaveCtx& ctx,
                                                 const double (&twc)[kTcCount], double (&twb)[kTbCount])
 {
-    ntt_inverse_r4_tw<BrSums, false, TWB_LOADED>(A, ctx, twc, twb);
-    lift_add<BrInverse::Out>(accj, A);           // centred lift, :258-281
+    ntt_inverse_r4_tw<BrSums, false, TWB_LOADED, BrInverse>(A, ctx, twc, twb);
+    lift_add_fp64<BrInverse::Out, kBrTrueMaxMilli>(accj, A);           // centred lift, :258-281
 }
 
 // descs[count]: in0/in1 are lvl0 TLWEs, out is a lvl1 TLWE (N+1 words, sample extract at

@@ -106,6 +106,23 @@ constexpr RegBounds gs_bounds(const RegBounds& in)
     }
     return out;
 }
+// The LAST pass of the inverse transform (stages 1-0: the HI pass in layout A), whose three twiddles are constants: w = 1/I = -I,
+// v = 1/zeta = -zeta^3 and v w = zeta^5 = -zeta.  Each product is one of the four-operation root products of fpfield.h, which
+// accept ANY value below 2^53 and leave a reduced one: only the sums have to fit (gs_bfly4_last).
+constexpr RegBounds gs_last_bounds(const RegBounds& in)
+{
+    RegBounds out{};
+    for (int g = 0; g < 4; g++) {
+        const double s0 = checked(in.v[reg_of<true>(g, 0, 0)] + in.v[reg_of<true>(g, 0, 1)]);
+        const double s1 = checked(in.v[reg_of<true>(g, 1, 0)] + in.v[reg_of<true>(g, 1, 1)]);
+        const bool fits = checked(s0 + s1) < kPoison && checked(s0 + fpf::AFTER_MUL_ROOT4) < kPoison;
+        out.v[reg_of<true>(g, 0, 0)] = checked(s0 + s1);
+        out.v[reg_of<true>(g, 1, 0)] = fits ? fpf::AFTER_MUL_ROOT4 : kPoison;
+        out.v[reg_of<true>(g, 0, 1)] = fits ? fpf::AFTER_MUL_ROOT8_CUBED : kPoison;
+        out.v[reg_of<true>(g, 1, 1)] = fits ? fpf::AFTER_MUL_ROOT8 : kPoison;
+    }
+    return out;
+}
 // Layout changes of ntt_wave.h.  A <-> B (through the LDS tile): all four register bits become lane bits.
 constexpr RegBounds xpose_all_bounds(const RegBounds& in) { return uniform(max_of(in)); }
 // B (reg = 4 h + m) -> C (reg = 4 m + g): h goes to the lanes, g comes from them
@@ -154,6 +171,10 @@ struct AfterCt {
 template <class S, bool HI>
 struct AfterGs {
     static constexpr RegBounds in() { return gs_bounds<HI>(S::in()); }
+};
+template <class S>
+struct AfterGsLast {
+    static constexpr RegBounds in() { return gs_last_bounds(S::in()); }
 };
 template <class S>
 struct AfterXposeAll {
@@ -240,6 +261,30 @@ struct Inverse {
     using Out = AfterGs<A1, true>;                                        // after stages 1-0
 };
 
+// The same transform with the root products in its last pass (gs_pass_hi_last) and its reductions placed register by register:
+// mask Mx names the registers reduced at each of the four places where Inverse sweeps by its limit.  A reduction is kept only
+// where a later sum would otherwise pass 2^53 -- the root products take any input, so nothing has to be small for THEM; the
+// pass-through register of the last pass is reduced by the lift that follows (Out::in() tells it which registers need that).
+// The masks belong to one input schedule S0 and are found for it by exhaustive search (tools/r4_reduction_search.cpp); a set
+// that does not fit poisons Out and fails the static_assert of the kernel.  With the masks the limit of Inverse gives for sums
+// of six rows (0x1111, 0x1111, 0x000e, 0x1111: 15 reductions) the passes before the last are those of Inverse.
+template <class S0, unsigned MC1, unsigned MB0, unsigned MB1, unsigned MA0>
+struct InverseRootTail {
+    static constexpr unsigned kMaskC1 = MC1, kMaskB0 = MB0, kMaskB1 = MB1, kMaskA0 = MA0;
+    using In = S0;
+    using C1 = AfterGs<S0, false>;                                        // after stages 9-8
+    using B0 = AfterXposeCB<AfterReduceMask<C1, MC1>>;
+    using B1 = AfterReduceMask<AfterGs<B0, false>, MB0>;              // after stages 7-6
+    using B2 = AfterReduceMask<AfterGs<B1, true>, MB1>;               // after stages 5-4
+    using A0 = AfterXposeAll<B2>;
+    using A1 = AfterReduceMask<AfterGs<A0, false>, MA0>;              // after stages 3-2
+    using Out = AfterGsLast<A1>;                                          // after stages 1-0
+};
+// The masks for S0 = PointwiseSum<FwdDigits<32>::Spectrum, 6, true>, the sums of blind_rotate_kernel: 12 reductions (the
+// fewest that fit; the limit of Inverse places 15).  The largest value on the way is 10.154 p of the 10.285 p a double holds.
+template <class S0>
+using InverseRootTail6x32 = InverseRootTail<S0, 0x0011u, 0x1111u, 0x000eu, 0x0111u>;
+
 // ---- the passes -------------------------------------------------------------------------------------------------
 template <bool WIDE>
 R4_HD double product(double a, double w) { return WIDE ? fpf::mulmod_wide(a, w) : fpf::mulmod(a, w); }
@@ -262,6 +307,16 @@ R4_HD void gs_bfly4(double& x0, double& xf, double& xc, double& xcf, double w, d
     xc = product<WC>(s0 - s1, w);
     xf = product<WF>(p - q, v);
     xcf = product<WCF>(p + q, vw);
+}
+// The last pass of the inverse: x_c' = -I (s0 - s1), x_f' = -zeta^3 (P - Q), x_cf' = -zeta (P + Q) with the signs taken
+// into the differences, so that the three products are by I, zeta^3 and zeta themselves (four operations each, no twiddle operand)
+R4_HD void gs_bfly4_last(double& x0, double& xf, double& xc, double& xcf)
+{
+    const double s0 = x0 + xf, np = xf - x0, s1 = xc + xcf, q = fpf::mul_root4(xc - xcf);
+    x0 = s0 + s1;
+    xc = fpf::mul_root4(s1 - s0);
+    xf = fpf::mul_root8_cubed(np + q);
+    xcf = fpf::mul_root8(np - q);
 }
 
 // One group of a pass, the wide / narrow choice of each product read from the schedule at compile time.
@@ -307,6 +362,16 @@ R4_HD void gs_pass_hi(double (&x)[16], const TW& tw)
     Group<S, true, 1>::gs(x, w, v, vw);
     Group<S, true, 2>::gs(x, w, v, vw);
     Group<S, true, 3>::gs(x, w, v, vw);
+}
+// the last pass of the inverse on schedule S (AfterGsLast<S> are its output bounds)
+template <class S>
+R4_HD void gs_pass_hi_last(double (&x)[16])
+{
+    static_assert(valid(gs_last_bounds(S::in())), "last inverse pass: a sum exceeds 2^53");
+    gs_bfly4_last(x[0], x[4], x[8], x[12]);
+    gs_bfly4_last(x[1], x[5], x[9], x[13]);
+    gs_bfly4_last(x[2], x[6], x[10], x[14]);
+    gs_bfly4_last(x[3], x[7], x[11], x[15]);
 }
 template <class S, int WB, int UB, class TW>
 R4_HD void gs_pass_lo(double (&x)[16], const TW& tw)

@@ -38,6 +38,7 @@
 //   pointwise: digits spectrum <= 6.18 -> each wide product <= 1.601, six of them 9.61 < 10.285
 #pragma once
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include "fpfield.h"
 #include "ntt_r4.h"
 #include "ntt_tables.h"
@@ -730,7 +731,7 @@ __device__ __forceinline__ void ntt_forward_digits_bc_r4(double (&x)[kRegs], con
     r4::ct_pass_lo<typename F::C1, 0, 4>(x, TwArr{twc});
 }
 
-template <class S0, bool HALF_TILE, bool TWB_LOADED>
+template <class S0, bool HALF_TILE, bool TWB_LOADED, class TAIL = void>
 __device__ __forceinline__ void ntt_inverse_r4_tw(double (&x)[kRegs], const WaveCtx& c, const double (&twc)[kTcCount], double (&twb)[kTbCount]);
 template <class S0, bool HALF_TILE = false>
 __device__ __forceinline__ void ntt_inverse_r4(double (&x)[kRegs], const WaveCtx& c)
@@ -742,9 +743,56 @@ __device__ __forceinline__ void ntt_inverse_r4(double (&x)[kRegs], const WaveCtx
 // The same with the twelve stage 9-8 twiddles already in registers (a caller with several inverse transforms in a row loads
 // them once, ahead of the work in front of the first); TWB_LOADED: the fifteen stage 7-4 twiddles as well, else they are
 // fetched here (into twb, which a following transform may then re-use)
-template <class S0, bool HALF_TILE, bool TWB_LOADED>
+// TAIL: an r4::InverseRootTail<S0, ..> instead of r4::Inverse<S0> -- the last pass multiplies by the roots -I, -zeta^3, -zeta with
+// the root products of fpfield.h (its three wave-uniform twiddles are not loaded), and the reductions between the passes are the
+// ones TAIL names register by register.  TAIL::Out::in() are then the output bounds.  Without it (void) the function is as it was.
+template <class V, bool TWB_LOADED>
+__device__ __forceinline__ void ntt_inverse_r4_root_tail(double (&x)[kRegs], const WaveCtx& c, const double (&twc)[kTcCount], double (&twb)[kTbCount])
+{
+    static_assert(r4::valid(V::Out::in()), "radix-4 inverse transform (root products in the last pass): a value exceeds 2^53");
+    r4::gs_pass_lo<typename V::In, 0, 4>(x, TwArr{twc});
+    r4::reduce_mask<V::kMaskC1>(x);
+    if (!TWB_LOADED) load_packed(twb, c.tb_inv);
+    xpose_cb_permlane(x);                            // C -> B in registers
+    r4::gs_pass_lo<typename V::B0, 3, 7>(x, TwArr{twb});
+    r4::reduce_mask<V::kMaskB0>(x);
+    // B -> A with every group of the pass stored as soon as it is computed, as in ntt_inverse_r4_tw
+    const double w = twb[0], v = twb[1], vw = twb[2];
+    double tu[15];                                   // stage 3-2 twiddles (wave-uniform, slots 3..14): scalar loads ahead of the pass
+#pragma unroll
+    for (int k = 3; k < 15; k++) tu[k] = c.gt->tu_inv[k];
+    asm volatile("" ::: "memory");
+    r4::Group<typename V::B1, true, 0>::gs(x, w, v, vw);
+    r4::reduce_mask<V::kMaskB1 & 0x1111u>(x);
+#pragma unroll
+    for (int k = 0; k < 16; k += 4) lds_st(c.b65, 32 * k, x[k]);
+    r4::Group<typename V::B1, true, 1>::gs(x, w, v, vw);
+    r4::reduce_mask<V::kMaskB1 & 0x2222u>(x);
+#pragma unroll
+    for (int k = 1; k < 16; k += 4) lds_st(c.b65, 32 * k, x[k]);
+    r4::Group<typename V::B1, true, 2>::gs(x, w, v, vw);
+    r4::reduce_mask<V::kMaskB1 & 0x4444u>(x);
+#pragma unroll
+    for (int k = 2; k < 16; k += 4) lds_st(c.b65, 32 * k, x[k]);
+    r4::Group<typename V::B1, true, 3>::gs(x, w, v, vw);
+    r4::reduce_mask<V::kMaskB1 & 0x8888u>(x);
+#pragma unroll
+    for (int k = 3; k < 16; k += 4) lds_st(c.b65, 32 * k, x[k]);
+    asm volatile("" ::: "memory");
+#pragma unroll
+    for (int r = 0; r < kRegs; r++) x[r] = lds_ld(c.a65, 8 * 65 * r);
+    r4::gs_pass_lo<typename V::A0, 3, 7>(x, TwArr{tu});
+    r4::reduce_mask<V::kMaskA0>(x);
+    r4::gs_pass_hi_last<typename V::A1>(x);
+}
+template <class S0, bool HALF_TILE, bool TWB_LOADED, class TAIL>
 __device__ __forceinline__ void ntt_inverse_r4_tw(double (&x)[kRegs], const WaveCtx& c, const double (&twc)[kTcCount], double (&twb)[kTbCount])
 {
+    if constexpr (!std::is_void<TAIL>::value) {
+        static_assert(!HALF_TILE && std::is_same<typename TAIL::In, S0>::value, "the root-product tail: full tile, and the schedule of this input");
+        ntt_inverse_r4_root_tail<TAIL, TWB_LOADED>(x, c, twc, twb);
+        return;
+    }
     using V = r4::Inverse<S0>;
     static_assert(r4::valid(V::Out::in()), "radix-4 inverse transform: a value exceeds 2^53");
     r4::gs_pass_lo<S0, 0, 4>(x, TwArr{twc});
@@ -792,6 +840,18 @@ __device__ __forceinline__ void ntt_inverse_r4_tw(double (&x)[kRegs], const Wave
     r4::gs_pass_lo<typename V::A0, 3, 7>(x, TwUniform{c.gt->tu_inv});
     r4::reduce_above<r4::AfterGs<typename V::A0, false>, V::kLimit>(x);
     r4::gs_pass_hi<typename V::A1>(x, TwUniform{c.gt->tu_inv});
+}
+// acc[r] += torus word of x[r] (the centred lift) in FP64 operations only -- v_mul_lo_u32, which lift_u32_small pays per word,
+// issues at a quarter of the rate.  A register whose bound proves that it holds its true value (at most TRUE_MAX_MILLI thousandths
+// of p in magnitude) takes the rounding add alone, any other is reduced first.
+template <class OUT, int TRUE_MAX_MILLI, int R = 0>
+__device__ __forceinline__ void lift_add_fp64(uint32_t (&acc)[kRegs], const double (&x)[kRegs])
+{
+    if constexpr (R < kRegs) {
+        if constexpr (fpf::lift_reduced_ok(OUT::in().v[R], TRUE_MAX_MILLI * 0.001)) acc[R] += fpf::lift_u32_reduced(x[R]);
+        else acc[R] += fpf::lift_u32(x[R]);
+        lift_add_fp64<OUT, TRUE_MAX_MILLI, R + 1>(acc, x);
+    }
 }
 // acc[r] += torus word of x[r] (the centred lift), the cheaper lift where the register's bound allows it
 template <class OUT, int R = 0>
