@@ -166,6 +166,8 @@ SIGNATURES = {
     "cufhe_amd_lvl2_keyswitch_batch": (ctypes.c_int, [ctypes.c_int, c_void, ctypes.c_size_t, c_void, c_void]),
     "cufhe_amd_lvl2_define_gate": (ctypes.c_int, [c_i32p, ctypes.c_uint32, c_void, ctypes.POINTER(ctypes.c_int)]),
     "cufhe_amd_lvl2_test_vector": (ctypes.c_int, [c_void, ctypes.c_int, c_void]),
+    "cufhe_amd_lvl2_define_gate_multi": (ctypes.c_int, [c_i32p, ctypes.c_uint32, ctypes.c_int, c_void, ctypes.POINTER(ctypes.c_int)]),
+    "cufhe_amd_lvl2_test_vector_multi": (ctypes.c_int, [c_void, ctypes.c_int, ctypes.c_int, c_void]),
     "cufhe_amd_lvl2_user_rotate_batch": (ctypes.c_int, [ctypes.c_int, c_void, ctypes.c_size_t, ctypes.c_int, c_void, c_void, c_void, ctypes.c_int,
                                                         c_void]),
     "cufhe_amd_lvl2_user_extract_batch": (ctypes.c_int, [ctypes.c_int, c_void, ctypes.c_size_t, ctypes.c_int, c_void, c_void, c_void, c_void]),

@@ -549,10 +549,16 @@ def lvl2_keyswitch_batch(tlwe2, tlwe0, count, device=0, stream=None):
 LVL2_USER_OP_BASE, LVL2_MAX_USER_GATES, LVL2_N = 8192, 64, 2048
 
 
-def lvl2_define_gate(coeffs, offset=0, test_vector=None):
+def lvl2_user_op_output(op, j):
+    """the op id of output j of multi-output lvl2 definition `op` (CUFHE_AMD_LVL2_USER_OP_OUTPUT)"""
+    return op + j * LVL2_MAX_USER_GATES
+
+
+def lvl2_define_gate(coeffs, offset=0, test_vector=None, nout=1):
     """A user gate of the N = 2048 ring: x = c0 in0 + c1 in1 + c2 in2 + (0, .., 0, offset) on lvl0 ciphertexts, bootstrapped through
     `test_vector` (2048 uint64 torus words; None: the constant 2^61).  Returns the op id: an op of lvl2_gate_batch, and of gate_batch /
-    Apply / gApply at level 0 while "lvl0_ring" is 2048."""
+    Apply / gApply at level 0 while "lvl0_ring" is 2048.  nout = 2, 4 or 8: a multi-output definition (interleaved test vector of
+    lvl2_test_vector_multi, required); output j is the op lvl2_user_op_output(op, j)."""
     c = np.zeros(3, dtype=np.int32)
     c[:len(coeffs)] = coeffs
     tv = None
@@ -561,6 +567,10 @@ def lvl2_define_gate(coeffs, offset=0, test_vector=None):
         if tv.size != LVL2_N:
             raise ValueError(f"test vector must have N2 = {LVL2_N} words")
     op = ctypes.c_int()
+    if nout != 1:
+        check(lib.cufhe_amd_lvl2_define_gate_multi(c.ctypes.data_as(_lib.c_i32p), int(offset) & 0xFFFFFFFF, int(nout),
+                                                   _ptr(tv) if tv is not None else None, ctypes.byref(op)))
+        return op.value
     check(lib.cufhe_amd_lvl2_define_gate(c.ctypes.data_as(_lib.c_i32p), int(offset) & 0xFFFFFFFF, _ptr(tv) if tv is not None else None,
                                          ctypes.byref(op)))
     return op.value
@@ -572,6 +582,17 @@ def lvl2_test_vector(values):
     v = np.ascontiguousarray(values, dtype=np.uint64)
     tv = np.empty(LVL2_N, dtype=np.uint64)
     check(lib.cufhe_amd_lvl2_test_vector(_ptr(v), int(v.size), _ptr(tv)))
+    return tv
+
+
+def lvl2_test_vector_multi(values):
+    """The interleaved 64-bit test vector of nout = len(values) functions (1, 2, 4 or 8) on p = len(values[0]) messages each,
+    p nout <= N2/2 (cufhe_amd_lvl2_test_vector_multi)."""
+    v = np.ascontiguousarray(values, dtype=np.uint64)
+    if v.ndim != 2:
+        raise ValueError("values must be [nout][p]")
+    tv = np.empty(LVL2_N, dtype=np.uint64)
+    check(lib.cufhe_amd_lvl2_test_vector_multi(_ptr(v), int(v.shape[1]), int(v.shape[0]), _ptr(tv)))
     return tv
 
 

@@ -88,7 +88,7 @@ struct DeviceState {
     double* bk2q_ntt = nullptr;        // the same key in the quarter layout
     bool br2q_lds_opt_in = false;
     uint32_t* ksk2 = nullptr;
-    uint64_t* tvs2 = nullptr;          // [kMaxUserGates2][k2N]: the lvl2 user gates' test vectors (cufhe_amd_lvl2_define_gate); CleanUp frees it
+    uint64_t* tvs2 = nullptr;          // [kTvRows2][k2N]: the lvl2 user gates' test vectors (cufhe_amd_lvl2_define_gate) and the library's own row (lvl2.inc.h: ensure_tvs2); CleanUp frees it
     uint32_t* cb_pksk = nullptr;       // circuit bootstrapping: the private key-switching key lvl2 -> lvl1 (cb.inc.h)
     uint32_t* pack_key = nullptr;      // TLWE packing: the lvl0 -> TRLWE key-switching key (pack.inc.h)
     std::vector<EventPair> br_events, ks_events;
@@ -116,6 +116,7 @@ plan::Tuning g_tuning;
 // "br_shape": 0 = by the rules of plan::plan_blind_rotate; 1 / 2 / 3 = every launch whole on the batch kernel (8 rotations per workgroup) / the
 // paired low-latency kernel (2 per workgroup) / the single one.  thread_local: the scheduler's launch worker picks a shape per launch.
 thread_local long g_br_shape = 0;
+long g_cb_rotations = 3;       // lvl02 rotations per circuit bootstrap: 3 (one per TRGSW row) or 1 (all rows from one rotation)
 long g_lvl0_ring = 1024;       // ring through which gates on lvl0 ciphertexts bootstrap: 1024 (lvl01/lvl10) or 2048 (lvl02/lvl20)
 constexpr int kMaxLogicalDevices = 64;    // SetGPUNum bound (per-device tables of fixed size: paramsets.inc.h)
 std::deque<DeviceState> g_dev(1);    // re-created only while no device is initialised (SetGPUNum)
@@ -492,24 +493,35 @@ bool is_seiks_at(int op) { return op >= CUFHE_AMD_TL_SEIKS_AT(0) && op <= CUFHE_
 bool is_cmux_rotate(int op) { return op >= CUFHE_AMD_TL_CMUX_ROTATE(0) && op <= CUFHE_AMD_TL_CMUX_ROTATE(2 * kN - 1); }
 int fail_packed_rom_set() { return fail(-1, "packed ROM words (TRLWE rotation, rotating CMUX, indexed SampleExtract) run on the default path only: not with \"param_set\" active"); }
 
-// User gates of the N = 2048 ring (cufhe_amd_lvl2_define_gate, lvl2.inc.h): definitions of their own in an id range of their own,
-// single output, 64-bit test vectors in row k of every device's DeviceState::tvs2.  Same write-once discipline as g_user.
+// User gates of the N = 2048 ring (cufhe_amd_lvl2_define_gate, _define_gate_multi, lvl2.inc.h): definitions of their own in an id range
+// of their own, 64-bit test vectors in row k of every device's DeviceState::tvs2.  Same write-once discipline as g_user; output j of a
+// multi-output definition k is CUFHE_AMD_LVL2_USER_OP_OUTPUT(base + k, j) = base + k + j * CUFHE_AMD_LVL2_MAX_USER_GATES.
 static_assert(CUFHE_AMD_LVL2_MAX_USER_GATES == kMaxUserGates2, "the header's capacity is the device table's");
 static_assert(CUFHE_AMD_LVL2_USER_OP_BASE > CUFHE_AMD_TL_CMUX_ROTATE(2 * kN - 1) && CUFHE_AMD_LVL2_USER_OP_BASE > CUFHE_AMD_TL_SEIKS_AT(kN - 1) &&
                   CUFHE_AMD_LVL2_USER_OP_BASE >= CUFHE_AMD_USER_OP_BASE + (kMaxUserGates << kMaxOutputShift) &&
                   CUFHE_AMD_LVL2_USER_OP_BASE > CUFHE_AMD_TL_CIRCUIT_BOOTSTRAP && CUFHE_AMD_LVL2_USER_OP_BASE >= CUFHE_AMD_NUM_OPS,
               "lvl2 user op ids lie above every other id range");
+static_assert(CUFHE_AMD_LVL2_USER_OP_OUTPUT(CUFHE_AMD_LVL2_USER_OP_BASE + kMaxUserGates2 - 1, (1 << kMaxOutputShift) - 1) ==
+                  CUFHE_AMD_LVL2_USER_OP_BASE + (kMaxUserGates2 << kMaxOutputShift) - 1, "lvl2 output ids fill [base, base + 8 * 64)");
 UserGate g_user2[kMaxUserGates2];
 std::atomic<int> g_user2_count{0};
-bool is_lvl2_user_op(int op) { return op >= CUFHE_AMD_LVL2_USER_OP_BASE && op < CUFHE_AMD_LVL2_USER_OP_BASE + kMaxUserGates2; }
-// the definition of `op`; nullptr when op is not a defined lvl2 user gate
+bool is_lvl2_user_op(int op) { return op >= CUFHE_AMD_LVL2_USER_OP_BASE && op < CUFHE_AMD_LVL2_USER_OP_BASE + (kMaxUserGates2 << kMaxOutputShift); }
+int lvl2_user_def(int op) { return (op - CUFHE_AMD_LVL2_USER_OP_BASE) % kMaxUserGates2; }      // definition index k of a lvl2 user op id
+int lvl2_user_output(int op) { return (op - CUFHE_AMD_LVL2_USER_OP_BASE) / kMaxUserGates2; }   // output j of a lvl2 user op id
+// the definition of `op`; nullptr when op is not a defined lvl2 user gate or names an output j >= nout of one
 const UserGate* lvl2_user_gate(int op)
 {
     if (!is_lvl2_user_op(op)) return nullptr;
-    const int k = op - CUFHE_AMD_LVL2_USER_OP_BASE;
-    return k < g_user2_count.load(std::memory_order_acquire) ? &g_user2[k] : nullptr;
+    const int k = lvl2_user_def(op);
+    if (k >= g_user2_count.load(std::memory_order_acquire)) return nullptr;
+    return lvl2_user_output(op) < g_user2[k].nout ? &g_user2[k] : nullptr;
 }
-int fail_lvl2_user_op() { return fail(-1, "lvl2 user gate op not defined (cufhe_amd_lvl2_define_gate; CleanUp drops the definitions)"); }
+// the refusal of a lvl2 user op id that names no defined gate: the messages of fail_user_op
+int fail_lvl2_user_op(int op)
+{
+    if (lvl2_user_output(op) == 0) return fail(-1, "lvl2 user gate op not defined (cufhe_amd_lvl2_define_gate; CleanUp drops the definitions)");
+    return fail(-1, "unknown gate op: not an output of a defined multi-output user gate (CUFHE_AMD_LVL2_USER_OP_OUTPUT(op, j), j < nout)");
+}
 int fail_lvl2_user_path()
 {
     return fail(-1, "lvl2 user gates run on the N = 2048 ring only: lvl0 ciphertexts through cufhe_amd_lvl2_gate_batch or with \"lvl0_ring\" 2048, "
@@ -564,9 +576,11 @@ long g_param_set = -1;
 //   lvl1_gates         whether it has gates on Mid ciphertexts (level 1)
 //   s, ready(), rotate(), keyswitch()   its device, the readiness check and the two launchers
 //   user_gates         whether its rotation kernels read LinDesc::pad as a test-vector row (user gates; the default path only)
-//   lvl2_user_gates    whether it runs the lvl2 user gates (RotDesc2::pad = kPadRow2 + row; the N = 2048 ring only); then rotate() takes
+//   lvl2_user_gates    whether it runs the lvl2 user gates (RotDesc2::pad = make_pad2(row, s); the N = 2048 ring only); then rotate() takes
 //                      one more argument: whether any descriptor names a row
 //   user_op(op), tv_pad(op, u)   the path's own definition lookup (nullptr: not a defined user gate of this path) and pad rule
+//   user_def(op), user_output(op), multi_pad(op, u)   definition index and output j of a user op id of the path, and the pad of a
+//                      multi-output definition's rotation (row and output shift)
 // Level 0: blind rotate -> key switch (__HomGate__ br -> iks); level 1: key switch -> blind rotate (iks -> br); Not / Copy and the
 // level-1 Mux sums run last, as one lincomb.  The three-input user gates' c0 in0 + c1 in1 run first, as one lincomb into temporaries.
 template <class P, class GetGate>
@@ -586,7 +600,7 @@ int lower_gates(const P& p, hipStream_t st, int level, size_t count, GetGate get
             const int op = get(g).op;
             if (!is_lvl2_user_op(op)) continue;
             if (g_param_set >= 0 || level != 0) return fail_lvl2_user_path();
-            if (!lvl2_user_gate(op)) return fail_lvl2_user_op();
+            if (!lvl2_user_gate(op)) return fail_lvl2_user_op(op);
         }
     }
     if (int rc = p.ready()) return rc;
@@ -606,30 +620,25 @@ int lower_gates(const P& p, hipStream_t st, int level, size_t count, GetGate get
     size_t nrot = 0, npre = 0;
     for (size_t g = 0; g < count; g++) {
         const int op = get(g).op;
-        if (is_user_op(op)) {
-            const UserGate* u = user_gate(op);
-            if (!u) return fail_user_op(op);
-            if (u->nout > 1) {
-                const GateRef gr = get(g);
-                const int arity = user_gate_arity(*u);
-                const auto key = std::make_tuple(user_def(op), (const uint32_t*)gr.in0, arity >= 2 ? gr.in1 : nullptr, arity == 3 ? gr.in2 : nullptr);
-                if (fuse.empty()) fuse.assign(count, (size_t)-1);
-                auto it = evals.find(key);
-                if (it == evals.end()) {
-                    it = evals.emplace(key, ev.size()).first;
-                    ev.push_back({nullptr, nullptr, false});
-                    nmulti_words += (size_t)u->nout;
-                    if (arity == 3) npre += 1;
+        if constexpr (P::user_gates || P::lvl2_user_gates) {
+            const UserGate* u = P::user_op(op);
+            if (P::user_gates && is_user_op(op) && !u) return fail_user_op(op);
+            if (u) {
+                if (u->nout > 1) {
+                    const GateRef gr = get(g);
+                    const int arity = user_gate_arity(*u);
+                    const auto key = std::make_tuple(P::user_def(op), (const uint32_t*)gr.in0, arity >= 2 ? gr.in1 : nullptr, arity == 3 ? gr.in2 : nullptr);
+                    if (fuse.empty()) fuse.assign(count, (size_t)-1);
+                    auto it = evals.find(key);
+                    if (it == evals.end()) {
+                        it = evals.emplace(key, ev.size()).first;
+                        ev.push_back({nullptr, nullptr, false});
+                        nmulti_words += (size_t)u->nout;
+                        if (arity == 3) npre += 1;
+                    }
+                    fuse[g] = it->second;
+                    continue;
                 }
-                fuse[g] = it->second;
-                continue;
-            }
-            nrot += 1;
-            if (user_gate_arity(*u) == 3) npre += 1;
-            continue;
-        }
-        if constexpr (P::lvl2_user_gates) {
-            if (const UserGate* u = P::user_op(op)) {
                 nrot += 1;
                 if (user_gate_arity(*u) == 3) npre += 1;
                 continue;
@@ -672,8 +681,8 @@ int lower_gates(const P& p, hipStream_t st, int level, size_t count, GetGate get
     for (size_t g = 0; g < count; g++) {
         const GateRef gr = get(g);
         if (!gr.out || !gr.in0) return fail(-1, "null ciphertext pointer");
-        if constexpr (P::user_gates) {
-            if (const UserGate* u = user_gate(gr.op); u && u->nout > 1) {
+        if constexpr (P::user_gates || P::lvl2_user_gates) {
+            if (const UserGate* u = P::user_op(gr.op); u && u->nout > 1) {
                 // output j of a multi-output evaluation: the evaluation's one rotation is emitted with its first requested output;
                 // level 0: the key switch of scratch output j into out; level 1: a copy of scratch output j into out (last lincomb)
                 const int arity = user_gate_arity(*u);
@@ -692,16 +701,17 @@ int lower_gates(const P& p, hipStream_t st, int level, size_t count, GetGate get
                         pre.push_back({gr.in0, gr.in1, t, u->c[0], u->c[1], 0u, 0u});
                         a = t; b = gr.in2; ca = 1; cb = u->c[2];
                     }
-                    const uint32_t pad = make_pad(user_def(gr.op), u->s);
+                    const uint32_t pad = P::multi_pad(gr.op, *u);
+                    tv_rows = true;
                     if (level == 0) {
                         rot.push_back({a, b, (Mid*)e.t1, ca, cb, u->off, pad});
-                    } else {
+                    } else if constexpr (P::lvl1_gates) {
                         e.t0 = tmpm0 + fuse[g] * P::lvl0_words;
                         ks.push_back({a, b, e.t0, ca, cb, u->off});
                         rot.push_back({e.t0, e.t0, (Mid*)e.t1, 1, 0, 0u, pad});
                     }
                 }
-                Mid* tj = (Mid*)e.t1 + (size_t)user_output(gr.op) * P::mid_words;
+                Mid* tj = (Mid*)e.t1 + (size_t)P::user_output(gr.op) * P::mid_words;
                 if (level == 0) ks.push_back({tj, tj, gr.out, 1, 0, 0u});
                 else lin.push_back({(const uint32_t*)tj, (const uint32_t*)tj, (uint32_t*)gr.out, 1, 0, 0u, 0u});
                 continue;
@@ -939,6 +949,9 @@ struct BasePath {
     static constexpr uint32_t ks_mu = kMu;
     static constexpr bool lvl1_gates = true, has_cmux = true, user_gates = true, packed_rom = true, lvl2_user_gates = false;
     static const UserGate* user_op(int op) { return user_gate(op); }
+    static int user_def(int op) { return ::user_def(op); }
+    static int user_output(int op) { return ::user_output(op); }
+    static uint32_t multi_pad(int op, const UserGate& u) { return make_pad(::user_def(op), u.s); }
     static uint32_t tv_pad(int op, const UserGate& u) { return u.tv ? (uint32_t)(op - CUFHE_AMD_USER_OP_BASE) + 1 : 0u; }
     static constexpr size_t trlwe_words = 2 * kN;
     static constexpr auto se_kernel = sample_extract_desc_kernel;
@@ -975,7 +988,7 @@ int run_gates(int device, void* stream, int level, size_t count, GetGate get)
         const int op = get(g).op;
         if (!is_lvl2_user_op(op)) continue;
         if (g_param_set >= 0 || level != 0 || g_lvl0_ring != 2048) return fail_lvl2_user_path();
-        if (!lvl2_user_gate(op)) return fail_lvl2_user_op();
+        if (!lvl2_user_gate(op)) return fail_lvl2_user_op(op);
     }
     if (level == 0 && g_lvl0_ring == 2048) return run_gates_lvl2(device, stream, count, get);
     if ((level == 0 || level == 1) && g_param_set >= 0) return run_gates_ps((int)g_param_set, device, stream, level, count, get);
@@ -1768,6 +1781,14 @@ int cufhe_amd_set_option(const char* key, long value)
         if (value < 0 || value > 2) return fail(-1, "sched_two_lane must be 0 (never), 1 (by the cost model) or 2 (whenever a flush is eligible)");
         g_sched_two_lane = value;
         sched_apply_settings();
+        return 0;
+    }
+    if (!strcmp(key, "cb_rotations")) {
+        // 3: one lvl02 rotation per TRGSW row (constant test vectors); 1: all l rows from one rotation (cb.inc.h)
+        if (value != 1 && value != 3) return fail(-1, "cb_rotations must be 3 (one rotation per TRGSW row) or 1 (all rows from one rotation)");
+        std::lock_guard<std::mutex> lk2(g_sched_mu);
+        if (int rc = sched_synchronize_all()) return rc;      // recorded circuit bootstraps complete in the form they were recorded under
+        g_cb_rotations = value;
         return 0;
     }
     if (!strcmp(key, "sched_rename")) {

@@ -1,5 +1,6 @@
 // cb.inc.h -- host side of circuit bootstrapping (included by capi.hip): lvl0 TLWE -> lvl1 TRGSW, torus or NTT domain.
-// Kernels: the lvl02 rotations of kernels_lvl2*.hip.h with RotDesc2::pad = log2 mu_r, cb_add_mu_kernel and private_keyswitch_kernel
+// Kernels: the lvl02 rotations of kernels_lvl2*.hip.h with RotDesc2::pad = log2 mu_r and cb_add_mu_kernel -- or, with "cb_rotations" 1,
+// one rotation per input from the library's test-vector row and cb_gather_mu_kernel -- and private_keyswitch_kernel
 // (kernels_pks.hip.h), bk_to_ntt_kernel for TRGSW2NTT.  Needs the lvl02 key (cufhe_amd_lvl2_initialize) and the private key-switching
 // key (cufhe_amd_cb_initialize); runs on the default parameter set only.
 
@@ -28,15 +29,37 @@ int launch_private_keyswitch(DeviceState& s, hipStream_t st, const uint64_t* in,
     return prof.commit();
 }
 
-// stage 1 of `count` circuit bootstraps: l rotations each, into tlwe2 [count][l][N2 + 1], mu_r added to b.  The descriptors come out of
-// `sc` (the caller's scratch: its other buffers stay valid)
-int cb_rotate(DeviceState& s, hipStream_t st, Scratch& sc, size_t count, const uint32_t* tlwe0, uint64_t* tlwe2)
+// scratch of stage 1 beside its result: the descriptors and, in the one-rotation form, the 2^kCbShift outputs of every rotation
+size_t cb_stage1_scratch(size_t count)
 {
+    if (g_cb_rotations == 1) return count * (sizeof(RotDesc2) + ((size_t)1 << kCbShift) * kPksIn * sizeof(uint64_t)) + 4096;
+    return count * kCbL * sizeof(RotDesc2) + 4096;
+}
+
+// stage 1 of `count` circuit bootstraps of the lvl0 ciphertexts in(g) into tlwe2 [count][l][N2 + 1], mu_r added to b: l rotations each
+// with constant test vectors, or ("cb_rotations" 1) one rotation each that leaves every row.  Descriptors and the one-rotation form's
+// outputs come out of `sc` (the caller's scratch, sized with cb_stage1_scratch: its other buffers stay valid)
+template <class GetIn>
+int cb_rotate(DeviceState& s, hipStream_t st, Scratch& sc, size_t count, GetIn in, uint64_t* tlwe2)
+{
+    RotDesc2* d;
+    if (g_cb_rotations == 1) {
+        if (int rc = ensure_tvs2(s)) return rc;
+        uint64_t* all;
+        if (int rc = sc.alloc((void**)&all, count * ((size_t)1 << kCbShift) * kPksIn * sizeof(uint64_t))) return rc;
+        std::vector<RotDesc2> h(count);
+        for (size_t g = 0; g < count; g++)
+            h[g] = RotDesc2{in(g), in(g), all + g * ((size_t)1 << kCbShift) * kPksIn, 1, 0, 0u, make_pad2(kCbRow2, kCbShift)};
+        if (int rc = upload_descs(s, sc, h, &d)) return rc;
+        if (int rc = launch_blind_rotate_lvl2(s, st, d, count, kLvl0N, nullptr, true)) return rc;
+        hipLaunchKernelGGL(cb_gather_mu_kernel, dim3((unsigned)(count * kCbL)), dim3(256), 0, st, all, tlwe2, (int)(count * kCbL));
+        HIP_TRY(hipGetLastError());
+        return 0;
+    }
     std::vector<RotDesc2> h(count * kCbL);
     for (size_t g = 0; g < count; g++)
         for (int r = 0; r < kCbL; r++)
-            h[g * kCbL + r] = RotDesc2{tlwe0 + g * kLvl0Words, tlwe0 + g * kLvl0Words, tlwe2 + (g * kCbL + r) * kPksIn, 1, 0, 0u, cb_mu_log2(r)};
-    RotDesc2* d;
+            h[g * kCbL + r] = RotDesc2{in(g), in(g), tlwe2 + (g * kCbL + r) * kPksIn, 1, 0, 0u, cb_mu_log2(r)};
     if (int rc = upload_descs(s, sc, h, &d)) return rc;
     if (int rc = launch_blind_rotate_lvl2(s, st, d, h.size(), kLvl0N, nullptr, false)) return rc;
     const int n = (int)h.size();
@@ -61,13 +84,13 @@ int cb_run(DeviceState& s, hipStream_t st, size_t count, const uint32_t* tlwe0, 
     if (count == 0) return 0;
     const size_t t2_bytes = count * kCbL * kPksIn * sizeof(uint64_t), tg_bytes = trgsw ? 0 : count * kCbTrgswWords * sizeof(uint32_t);
     Scratch sc;
-    if (int rc = open_scratch(s, st, t2_bytes + tg_bytes + count * kCbL * sizeof(RotDesc2) + 8192, &sc)) return rc;
+    if (int rc = open_scratch(s, st, t2_bytes + tg_bytes + cb_stage1_scratch(count) + 8192, &sc)) return rc;
     uint64_t* t2;
     if (int rc = sc.alloc((void**)&t2, t2_bytes)) return rc;
     uint32_t* tg = trgsw;
     if (!tg)
         if (int rc = sc.alloc((void**)&tg, tg_bytes)) return rc;
-    if (int rc = cb_rotate(s, st, sc, count, tlwe0, t2)) return rc;
+    if (int rc = cb_rotate(s, st, sc, count, [&](size_t g) { return tlwe0 + g * kLvl0Words; }, t2)) return rc;
     if (int rc = launch_private_keyswitch(s, st, t2, count * kCbL, tg, kCbL)) return rc;
     return trgsw_ntt ? cb_to_ntt(s, st, count, tg, trgsw_ntt) : 0;
 }
@@ -85,20 +108,13 @@ int lower_cb_ops(DeviceState& s, hipStream_t st, const GateRef* g, size_t n)
     const size_t count = ins.size();
     const size_t t2_bytes = count * kCbL * kPksIn * sizeof(uint64_t), tg_bytes = count * kCbTrgswWords * sizeof(uint32_t);
     Scratch sc;
-    if (int rc = open_scratch(s, st, t2_bytes + tg_bytes + count * (kCbL * sizeof(RotDesc2) + kBkPolysPerStep * sizeof(LinDesc)) + 16384, &sc))
+    if (int rc = open_scratch(s, st, t2_bytes + tg_bytes + cb_stage1_scratch(count) + count * kBkPolysPerStep * sizeof(LinDesc) + 16384, &sc))
         return rc;
     uint64_t* t2;
     uint32_t* tg;
     if (int rc = sc.alloc((void**)&t2, t2_bytes)) return rc;
     if (int rc = sc.alloc((void**)&tg, tg_bytes)) return rc;
-    std::vector<RotDesc2> h(count * kCbL);
-    for (size_t c = 0; c < count; c++)
-        for (int r = 0; r < kCbL; r++) h[c * kCbL + r] = RotDesc2{ins[c], ins[c], t2 + (c * kCbL + r) * kPksIn, 1, 0, 0u, cb_mu_log2(r)};
-    RotDesc2* d;
-    if (int rc = upload_descs(s, sc, h, &d)) return rc;
-    if (int rc = launch_blind_rotate_lvl2(s, st, d, h.size(), kLvl0N, nullptr, false)) return rc;
-    hipLaunchKernelGGL(cb_add_mu_kernel, dim3((unsigned)((h.size() + 255) / 256)), dim3(256), 0, st, t2, (int)h.size());
-    HIP_TRY(hipGetLastError());
+    if (int rc = cb_rotate(s, st, sc, count, [&](size_t c) { return ins[c]; }, t2)) return rc;
     if (int rc = launch_private_keyswitch(s, st, t2, count * kCbL, tg, kCbL)) return rc;
     // TRGSW2NTT into the holders: contiguous runs of holders are one launch of the batch conversion; scattered ones one launch each
     size_t a = 0;
@@ -140,6 +156,7 @@ int cufhe_amd_cb_initialize(const uint32_t* privksk, size_t words)
     for (int i = 0; i < g_gpu_num; i++) {
         if (int rc = ensure_ntt(i)) return rc;
         HIP_TRY(hipSetDevice(phys_device(i)));
+        if (int rc = ensure_tvs2(g_dev[i])) return rc;        // the one-rotation form's test-vector row
         HIP_TRY(built[(size_t)i].alloc(kPksKeyWords));
         const char* src = (const char*)privksk;
         char* dst = (char*)built[(size_t)i].p;
@@ -168,8 +185,8 @@ int cufhe_amd_cb_rotate_batch(int device, void* stream, size_t count, const uint
     if (count == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     Scratch sc;
-    if (int rc = open_scratch(s, st, count * kCbL * sizeof(RotDesc2) + 4096, &sc)) return rc;
-    return cb_rotate(s, st, sc, count, tlwe0, tlwe2);
+    if (int rc = open_scratch(s, st, cb_stage1_scratch(count) + 4096, &sc)) return rc;
+    return cb_rotate(s, st, sc, count, [&](size_t g) { return tlwe0 + g * kLvl0Words; }, tlwe2);
 }
 
 int cufhe_amd_private_keyswitch_batch(int device, void* stream, size_t count, const uint64_t* tlwe2, uint32_t* trlwe)

@@ -70,15 +70,24 @@ struct RotDesc2 {          // lvl0 operands, lvl2 result (sample-extracted TLWE)
     int32_t ca, cb;
     uint32_t off;
     uint32_t pad;          // test vector: 0 = the constant k2Mu, 1..63 = the constant 2^pad (circuit bootstrapping: desc_mu2),
-                           // kPadRow2 + row = row `row` of the lvl2 user gates' table (cufhe_amd_lvl2_define_gate)
+                           // make_pad2(row, s) = row `row` of the lvl2 user gates' table (cufhe_amd_lvl2_define_gate) with 2^s outputs
 };
 __host__ __device__ constexpr uint64_t desc_mu2(uint32_t pad) { return pad ? 1ull << (pad & 63) : k2Mu; }
-// lvl2 user gates: the rotation starts from (0, X^bbar TV), TV a row of tvs[kMaxUserGates2][k2N].  Only the <true> instantiations of
+// lvl2 user gates: the rotation starts from (0, X^bbar TV), TV a row of tvs[kTvRows2][k2N].  Only the <true> instantiations of
 // the two rotation kernels read the table; a launch whose descriptors name no row runs <false>, the kernels as they were.
+// A descriptor that names a row also carries an output shift s in bits 8-9 (make_pad2, as make_pad on the default path): the modulus
+// switch rounds to multiples of 2^s and the rotation extracts 2^s outputs, SampleExtract(j) for j < 2^s, as contiguous lvl2 TLWEs
+// at `out`.  s = 0 is the single-output rotation.  Row kCbRow2, behind the users' rows, is the library's own: the test vector of the
+// one-rotation circuit bootstrap (cb.inc.h).
 constexpr int kMaxUserGates2 = 64;
+constexpr int kCbRow2 = kMaxUserGates2;
+constexpr int kTvRows2 = kMaxUserGates2 + 1;
 constexpr uint32_t kPadRow2 = 64;
 static_assert(kPadRow2 > 63, "rows lie above every constant pad");
 __host__ __device__ constexpr bool desc_has_row2(uint32_t pad) { return pad >= kPadRow2; }
+__host__ __device__ constexpr uint32_t make_pad2(int row, int s) { return (kPadRow2 + (uint32_t)row) | ((uint32_t)s << 8); }
+__host__ __device__ constexpr uint32_t desc_shift2(uint32_t pad) { return desc_has_row2(pad) ? (pad >> 8) & 3u : 0u; }
+static_assert(kPadRow2 + kTvRows2 - 1 < 256 && make_pad2(kCbRow2, 3) - kPadRow2 - (3u << 8) == (uint32_t)kCbRow2, "row and shift do not overlap");
 // coefficient e of X^bbar TV in Z[X]/(X^2048 + 1), 1 <= bbar <= 2 N: TV[(e - bbar) mod N], negated where the exponent wraps an odd
 // number of times; bbar = 2 N is the identity
 __device__ __forceinline__ uint64_t rotated_tv_coef2(const uint64_t* __restrict__ tv, uint32_t bbar, uint32_t e)
@@ -89,7 +98,21 @@ __device__ __forceinline__ uint64_t rotated_tv_coef2(const uint64_t* __restrict_
 }
 __device__ __forceinline__ const uint64_t* desc_tv2(const uint64_t* __restrict__ tvs, uint32_t pad)
 {
-    return tvs + (size_t)((pad - kPadRow2) & (kMaxUserGates2 - 1)) * k2N;
+    return tvs + (size_t)((pad - kPadRow2) & (2 * kMaxUserGates2 - 1)) * k2N;
+}
+// the modulus switch of a descriptor with output shift s: abar_i and bbar are multiples of 2^s (s = 0: the plain switch)
+__device__ __forceinline__ uint16_t ms_abar2(uint32_t c, uint32_t s) { return (uint16_t)(((c + (1u << (32 - 2 - k2Nbit + s))) >> (32 - 1 - k2Nbit + s)) << s); }
+__device__ __forceinline__ uint32_t ms_bbar2(uint32_t c, uint32_t s) { return 2 * k2N - ((c >> (32 - 1 - k2Nbit + s)) << s); }
+// SampleExtract(j) of accumulator word (component, position e) = v into the lvl2 TLWE o: a[e] goes to o[j - e] for e <= j and, negated,
+// to o[N2 + j - e] for e > j; b[j] is the last word.  Every position writes exactly one word of [0, N2) and position j one more.
+__device__ __forceinline__ void extract_word2(uint64_t* __restrict__ o, int j, int component, int e, uint64_t v)
+{
+    if (component) {
+        if (e == j) o[k2N] = v;
+    } else {
+        if (e <= j) o[j - e] = v;
+        else o[k2N + j - e] = 0ull - v;
+    }
 }
 struct LinDesc64 {         // out(lvl0) = KS(ca * in0 + cb * in1 + (0, .., off)) on lvl2 TLWEs
     const uint64_t* in0;
@@ -284,8 +307,14 @@ __global__ __launch_bounds__(k2Threads) void blind_rotate_lvl2_kernel(
     const RotDesc2 d = descs[g];
     for (int i = tid; i <= kLvl0N; i += k2Threads) {
         const uint32_t c = (uint32_t)d.ca * d.in0[i] + (uint32_t)d.cb * d.in1[i];
-        if (i < kLvl0N) abar_lds[i] = (uint16_t)((c + (1u << (32 - 2 - k2Nbit))) >> (32 - 1 - k2Nbit));
-        else *bbar_slot = 2 * k2N - ((c + d.off) >> (32 - 1 - k2Nbit));
+        if constexpr (TV) {
+            const uint32_t sh = desc_shift2(d.pad);
+            if (i < kLvl0N) abar_lds[i] = ms_abar2(c, sh);
+            else *bbar_slot = ms_bbar2(c + d.off, sh);
+        } else {
+            if (i < kLvl0N) abar_lds[i] = (uint16_t)((c + (1u << (32 - 2 - k2Nbit))) >> (32 - 1 - k2Nbit));
+            else *bbar_slot = 2 * k2N - ((c + d.off) >> (32 - 1 - k2Nbit));
+        }
     }
     for (int i = tid; i < 2 * k3SumDoubles; i += k2Threads) sumL[i] = 0.0;
     for (int i = tid; i < 2 * 2 * kTbCount * 16; i += k2Threads) {     // tb_fwd and tb_inv are contiguous in NttTables
@@ -591,6 +620,22 @@ __global__ __launch_bounds__(k2Threads) void blind_rotate_lvl2_kernel(
                 if (e0 == 0) o[0] = acc_lo[m];
                 else o[k2N - e0] = 0ull - acc_lo[m];
                 o[k2N - e1] = 0ull - acc_hi[m];
+            }
+        }
+    }
+    if constexpr (TV) {
+        // The further outputs of a multi-output descriptor: SampleExtract(j), j = 1 .. 2^s - 1, read from the copy of the accumulator
+        // that publish_acc left in LDS (component c at sum polynomials (c, 3 c), (c, 3 c + 1)), one word per thread and pass: the
+        // accumulator registers do not stay live for it and the writes are contiguous.  d is uniform: so is the barrier.
+        const int nout = 1 << desc_shift2(d.pad);
+        if (d.out && nout > 1) {
+            __syncthreads();                                  // every owner's last copy is in LDS
+            const uint64_t* a = (const uint64_t*)(smem + k3LdsSum);
+            const uint64_t* b = (const uint64_t*)(smem + k3LdsSum + (k3SumDoubles + 3 * k2Half) * 8);
+            for (int j = 1; j < nout; j++) {
+                uint64_t* oj = d.out + (size_t)j * k2Words;
+                for (int k = tid; k < k2N; k += k2Threads) oj[k] = k <= j ? a[j - k] : 0ull - a[k2N + j - k];
+                if (tid == 0) oj[k2N] = b[j];
             }
         }
     }

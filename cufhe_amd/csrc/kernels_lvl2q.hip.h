@@ -342,8 +342,14 @@ __global__ __launch_bounds__(kQThreads, 2) void blind_rotate_lvl2q_kernel(
     const RotDesc2 d = descs[g];
     for (int i = tid; i <= kLvl0N; i += kQThreads) {
         const uint32_t c = (uint32_t)d.ca * d.in0[i] + (uint32_t)d.cb * d.in1[i];
-        if (i < kLvl0N) abar_lds[i] = (uint16_t)((c + (1u << (32 - 2 - k2Nbit))) >> (32 - 1 - k2Nbit));
-        else *bbar_slot = 2 * k2N - ((c + d.off) >> (32 - 1 - k2Nbit));
+        if constexpr (TV) {
+            const uint32_t sh = desc_shift2(d.pad);
+            if (i < kLvl0N) abar_lds[i] = ms_abar2(c, sh);
+            else *bbar_slot = ms_bbar2(c + d.off, sh);
+        } else {
+            if (i < kLvl0N) abar_lds[i] = (uint16_t)((c + (1u << (32 - 2 - k2Nbit))) >> (32 - 1 - k2Nbit));
+            else *bbar_slot = 2 * k2N - ((c + d.off) >> (32 - 1 - k2Nbit));
+        }
     }
     for (int i = tid; i < kQWaves * kQTabDoubles; i += kQThreads) {
         const int q = i / kQTabDoubles, k = i % kQTabDoubles;
@@ -653,6 +659,18 @@ __global__ __launch_bounds__(kQThreads, 2) void blind_rotate_lvl2q_kernel(
                     o[k2N - e] = 0ull - acc[0][s][t];
                 }
             }
+        if constexpr (TV) {   // the further outputs of a multi-output descriptor, from the same registers
+            const int nout = 1 << desc_shift2(d.pad);
+            for (int j = 1; j < nout; j++) {
+                uint64_t* oj = d.out + (size_t)j * k2Words;
+#pragma unroll
+                for (int c = 0; c < 2; c++)
+#pragma unroll
+                    for (int s = 0; s < 2; s++)
+#pragma unroll
+                        for (int t = 0; t < 4; t++) extract_word2(oj, j, c, e_base + 64 * s + kQPoints * t, acc[c][s][t]);
+            }
+        }
     }
 #undef CUFHE_AMD_PHASEQ
 }

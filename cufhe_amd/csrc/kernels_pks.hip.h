@@ -33,6 +33,21 @@ __global__ __launch_bounds__(256) void cb_add_mu_kernel(uint64_t* __restrict__ t
     if (x < n) tlwe2[(size_t)x * kPksIn + k2N] += 1ull << cb_mu_log2(x % kCbL);
 }
 
+// The one-rotation form ("cb_rotations" 1): one rotation per input from the library's test-vector row (kCbRow2: TV[4 q + r] = mu_r,
+// TV[4 q + 3] = 0) with output shift kCbShift = 2 leaves SampleExtract(0 .. 3) in all[count][4][N2 + 1]; row r < l of input g goes to
+// tlwe2[g][r] with mu_r added to b.  One workgroup per row.
+constexpr int kCbShift = 2;
+static_assert((1 << kCbShift) > kCbL, "the rows of one TRGSW fit the outputs of one rotation");
+__global__ __launch_bounds__(256) void cb_gather_mu_kernel(const uint64_t* __restrict__ all, uint64_t* __restrict__ tlwe2, int rows)
+{
+    const int x = blockIdx.x;
+    if (x >= rows) return;
+    const int g = x / kCbL, r = x % kCbL;
+    const uint64_t* src = all + ((size_t)g * (1 << kCbShift) + r) * kPksIn;
+    uint64_t* dst = tlwe2 + (size_t)x * kPksIn;
+    for (int i = threadIdx.x; i < kPksIn; i += 256) dst[i] = src[i] + (i == k2N ? 1ull << cb_mu_log2(r) : 0ull);
+}
+
 // Private key switch.  Input x (a lvl2 TLWE) and key function u give the TRLWE
 //     0 - sum_i sum_j [a_ij != 0] K_u[i][j][a_ij - 1],   a_ij = ((tlwe2[i] + 2^33) >> (64 - 3 (j + 1))) & 7,
 // written to out + (x / L) (2 L) 2N + (u L + x % L) 2N (L = rows_per_out: 3 for a TRGSW, 1 for the stand-alone entry point).

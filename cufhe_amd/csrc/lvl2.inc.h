@@ -62,6 +62,24 @@ void lvl2_release_host_key()
     std::vector<uint64_t>().swap(g_bk2_host);
 }
 
+// The ring's table of test vectors on device `device`: kMaxUserGates2 rows of the users' definitions and, behind them, the library's own
+// row kCbRow2 -- the test vector of the one-rotation circuit bootstrap, TV[4 q + r] = 2^(63 - 6 (r + 1)) for r < l = 3 and TV[4 q + 3] = 0.
+// Allocated with the first definition, by cufhe_amd_cb_initialize or by the first one-rotation circuit bootstrap; CleanUp frees it.
+// The device of `s` is the calling thread's current device.
+std::mutex g_tvs2_mu;
+int ensure_tvs2(DeviceState& s)
+{
+    std::lock_guard<std::mutex> lk(g_tvs2_mu);
+    if (s.tvs2) return 0;
+    DevPtr<uint64_t> t;
+    HIP_TRY(t.alloc((size_t)kTvRows2 * k2N));
+    std::vector<uint64_t> row((size_t)k2N);
+    for (int i = 0; i < k2N; i++) row[(size_t)i] = (i & 3) < 3 ? 1ull << (63 - 6 * ((i & 3) + 1)) : 0ull;
+    HIP_TRY(hipMemcpy(t.p + (size_t)kCbRow2 * k2N, row.data(), k2N * sizeof(uint64_t), hipMemcpyHostToDevice));
+    s.tvs2 = t.release();
+    return 0;
+}
+
 // tv_rows: a descriptor names a row of the lvl2 user gates' table (pad >= kPadRow2): the launch runs the <true> instantiation, which
 // also handles constant pads; every other launch (built-in gates, circuit bootstrapping) runs <false>, the kernels as they were
 int launch_blind_rotate_lvl2(DeviceState& s, hipStream_t st, const RotDesc2* d, size_t count, int steps, uint64_t* acc_dump, bool tv_rows)
@@ -117,7 +135,10 @@ struct Lvl2Path {
     static constexpr bool lvl1_gates = false, user_gates = false, lvl2_user_gates = true;
     // the ring's own definitions (cufhe_amd_lvl2_define_gate): an op of cufhe_amd_define_gate stays refused here
     static const UserGate* user_op(int op) { return lvl2_user_gate(op); }
-    static uint32_t tv_pad(int op, const UserGate& u) { return u.tv ? kPadRow2 + (uint32_t)(op - CUFHE_AMD_LVL2_USER_OP_BASE) : 0u; }
+    static uint32_t tv_pad(int op, const UserGate& u) { return u.tv ? make_pad2(lvl2_user_def(op), 0) : 0u; }
+    static int user_def(int op) { return lvl2_user_def(op); }
+    static int user_output(int op) { return lvl2_user_output(op); }
+    static uint32_t multi_pad(int op, const UserGate& u) { return make_pad2(lvl2_user_def(op), u.s); }
     DeviceState& s;
     int ready() const { return s.keys2_ready ? 0 : fail(-3, "cufhe_amd_lvl2_initialize has not been called for this device"); }
     int rotate(hipStream_t st, const RotDesc2* d, size_t count, int steps, uint64_t* dump, bool tv_rows) const { return launch_blind_rotate_lvl2(s, st, d, count, steps, dump, tv_rows); }
@@ -133,7 +154,9 @@ int run_gates_lvl2(int device, void* stream, size_t count, GetGate get)
 
 // The parity hooks of the lvl2 user gates: `count` evaluations of definition `op` on [count][n + 1] arrays, with the rotation
 // descriptors of the gate path (lower_gates: arity, the pre-added c0 in0 + c1 in1 of three operands, the pad) and another tail: the
-// accumulator after `steps` steps (acc), or the sample-extracted lvl2 TLWE without its key switch (tlwe2).
+// accumulator after `steps` steps (acc), or the sample-extracted lvl2 TLWE without its key switch (tlwe2).  Of a multi-output
+// definition acc takes output 0's id (the one accumulator); tlwe2 takes any output id: the rotations write all nout outputs to scratch
+// and output j alone is copied to the caller's [count][N2 + 1].
 int lvl2_user_rotations(int device, void* stream, size_t count, int op, const uint32_t* in0, const uint32_t* in1, const uint32_t* in2,
                         int steps, uint64_t* acc, uint64_t* tlwe2)
 {
@@ -142,7 +165,9 @@ int lvl2_user_rotations(int device, void* stream, size_t count, int op, const ui
     if (!is_lvl2_user_op(op)) return fail(-1, "op is not in the lvl2 user gates' id range (CUFHE_AMD_LVL2_USER_OP_BASE + k)");
     if (g_param_set >= 0) return fail_lvl2_user_path();
     const UserGate* u = lvl2_user_gate(op);
-    if (!u) return fail_lvl2_user_op();
+    if (!u) return fail_lvl2_user_op(op);
+    const int out_j = lvl2_user_output(op);
+    if (acc && out_j != 0) return fail(-1, "the accumulator of a multi-output definition is dumped under output 0's id");
     if (!s.keys2_ready) return fail(-3, "cufhe_amd_lvl2_initialize has not been called for this device");
     if (!in0 || (!acc && !tlwe2)) return fail(-1, "null pointer");
     const int arity = user_gate_arity(*u);
@@ -151,11 +176,17 @@ int lvl2_user_rotations(int device, void* stream, size_t count, int op, const ui
     if (count == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     Scratch sc;
-    if (int rc = open_scratch(s, st, count * (sizeof(RotDesc2) + sizeof(LinDesc) + (arity == 3 ? kLvl0Words * sizeof(uint32_t) : 0)) + 4096, &sc)) return rc;
+    const bool multi = u->nout > 1;
+    const size_t multi_bytes = multi && tlwe2 ? count * (size_t)u->nout * k2Words * sizeof(uint64_t) : 0;
+    if (int rc = open_scratch(s, st, multi_bytes + count * (sizeof(RotDesc2) + 2 * sizeof(LinDesc) + (arity == 3 ? kLvl0Words * sizeof(uint32_t) : 0)) + 8192, &sc))
+        return rc;
     uint32_t* tmpp = nullptr;
     if (arity == 3)
         if (int rc = sc.alloc((void**)&tmpp, count * kLvl0Words * sizeof(uint32_t))) return rc;
-    const uint32_t pad = Lvl2Path::tv_pad(op, *u);
+    uint64_t* all = nullptr;          // a multi-output definition: [count][nout][N2 + 1], of which output out_j reaches tlwe2
+    if (multi_bytes)
+        if (int rc = sc.alloc((void**)&all, multi_bytes)) return rc;
+    const uint32_t pad = multi ? Lvl2Path::multi_pad(op, *u) : Lvl2Path::tv_pad(op, *u);
     std::vector<RotDesc2> rot(count);
     std::vector<LinDesc> pre;
     for (size_t g = 0; g < count; g++) {
@@ -167,14 +198,25 @@ int lvl2_user_rotations(int device, void* stream, size_t count, int op, const ui
             pre.push_back({a, b, t, u->c[0], u->c[1], 0u, 0u});
             a = t; b = in2 + g * kLvl0Words; ca = 1; cb = u->c[2];
         }
-        rot[g] = RotDesc2{a, b, tlwe2 ? tlwe2 + g * k2Words : nullptr, ca, cb, u->off, pad};
+        uint64_t* o = !tlwe2 ? nullptr : multi ? all + g * (size_t)u->nout * k2Words : tlwe2 + g * k2Words;
+        rot[g] = RotDesc2{a, b, o, ca, cb, u->off, pad};
     }
     RotDesc2* drot;
     LinDesc* dpre;
     if (int rc = upload_descs(s, sc, rot, &drot)) return rc;
     if (int rc = upload_descs(s, sc, pre, &dpre)) return rc;
     if (int rc = launch_lincomb(st, dpre, pre.size(), kLvl0Words)) return rc;
-    return launch_blind_rotate_lvl2(s, st, drot, count, steps, acc, pad != 0);
+    if (int rc = launch_blind_rotate_lvl2(s, st, drot, count, steps, acc, pad != 0)) return rc;
+    if (!all) return 0;
+    // output out_j of every evaluation: a copy of 2 (N2 + 1) 32-bit words
+    std::vector<LinDesc> cp(count);
+    for (size_t g = 0; g < count; g++) {
+        const uint32_t* src = (const uint32_t*)(all + (g * (size_t)u->nout + (size_t)out_j) * k2Words);
+        cp[g] = LinDesc{src, src, (uint32_t*)(tlwe2 + g * k2Words), 1, 0, 0u, 0u};
+    }
+    LinDesc* dcp;
+    if (int rc = upload_descs(s, sc, cp, &dcp)) return rc;
+    return launch_lincomb(st, dcp, cp.size(), 2 * k2Words);
 }
 
 }  // namespace
@@ -251,9 +293,9 @@ int cufhe_amd_lvl2_gate_batch(int device, void* stream, size_t count, const int3
     });
 }
 
-int cufhe_amd_lvl2_define_gate(const int32_t coeffs[3], uint32_t offset, const uint64_t* test_vector, int* op)
+// definition k = g_user2_count of a lvl2 user gate with nout = 2^sh outputs (1: cufhe_amd_lvl2_define_gate); the caller holds g_mu
+static int define_lvl2_user_gate(const int32_t coeffs[3], uint32_t offset, const uint64_t* test_vector, int sh, int* op)
 {
-    std::lock_guard<std::mutex> lk(g_mu);
     if (!coeffs || !op) return fail(-1, "null pointer");
     if (coeffs[0] == 0) return fail(-1, "lvl2 user gate: c0 must not be 0");
     if (g_param_set >= 0) return fail(-1, "lvl2 user gates run on the N = 2048 ring only: not while \"param_set\" is active");
@@ -261,26 +303,35 @@ int cufhe_amd_lvl2_define_gate(const int32_t coeffs[3], uint32_t offset, const u
         if (!g_dev[i].keys2_ready) return fail(-3, "cufhe_amd_lvl2_initialize has not been called for every device");
     const int k = g_user2_count.load(std::memory_order_relaxed);
     if (k >= kMaxUserGates2) return fail(-1, "lvl2 user gate table full (CUFHE_AMD_LVL2_MAX_USER_GATES definitions until CleanUp)");
-    // build first, swap last: the tables of the devices that have none yet are all allocated before any is installed; row k of every
-    // table is written synchronously, and no launch reads the row before its id exists
-    std::vector<DevPtr<uint64_t>> fresh((size_t)g_gpu_num);
+    // every device's table exists before any row is written; row k of every table is written synchronously, and no launch reads the
+    // row before its id exists
     for (int i = 0; i < g_gpu_num; i++) {
-        if (g_dev[i].tvs2) continue;
         HIP_TRY(hipSetDevice(phys_device(i)));
-        HIP_TRY(fresh[(size_t)i].alloc((size_t)kMaxUserGates2 * k2N));
+        if (int rc = ensure_tvs2(g_dev[i])) return rc;
     }
     if (test_vector)
         for (int i = 0; i < g_gpu_num; i++) {
-            uint64_t* t = g_dev[i].tvs2 ? g_dev[i].tvs2 : fresh[(size_t)i].p;
             HIP_TRY(hipSetDevice(phys_device(i)));
-            HIP_TRY(hipMemcpy(t + (size_t)k * k2N, test_vector, k2N * sizeof(uint64_t), hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(g_dev[i].tvs2 + (size_t)k * k2N, test_vector, k2N * sizeof(uint64_t), hipMemcpyHostToDevice));
         }
-    for (int i = 0; i < g_gpu_num; i++)
-        if (!g_dev[i].tvs2) g_dev[i].tvs2 = fresh[(size_t)i].release();
-    g_user2[k] = UserGate{{coeffs[0], coeffs[1], coeffs[2]}, offset, test_vector != nullptr, 1, 0};
+    g_user2[k] = UserGate{{coeffs[0], coeffs[1], coeffs[2]}, offset, test_vector != nullptr, 1 << sh, sh};
     g_user2_count.store(k + 1, std::memory_order_release);
     *op = CUFHE_AMD_LVL2_USER_OP_BASE + k;
     return 0;
+}
+
+int cufhe_amd_lvl2_define_gate(const int32_t coeffs[3], uint32_t offset, const uint64_t* test_vector, int* op)
+{
+    std::lock_guard<std::mutex> lk(g_mu);
+    return define_lvl2_user_gate(coeffs, offset, test_vector, 0, op);
+}
+
+int cufhe_amd_lvl2_define_gate_multi(const int32_t coeffs[3], uint32_t offset, int nout, const uint64_t* test_vector, int* op)
+{
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (nout != 2 && nout != 4 && nout != 8) return fail(-1, "multi-output lvl2 user gate: nout must be 2, 4 or 8");
+    if (!test_vector) return fail(-1, "multi-output lvl2 user gate: the test vector is required (cufhe_amd_lvl2_test_vector_multi)");
+    return define_lvl2_user_gate(coeffs, offset, test_vector, nout == 2 ? 1 : nout == 4 ? 2 : 3, op);
 }
 
 int cufhe_amd_lvl2_test_vector(const uint64_t* values, int p, uint64_t* tv)
@@ -292,6 +343,23 @@ int cufhe_amd_lvl2_test_vector(const uint64_t* values, int p, uint64_t* tv)
     for (int j = 0; j < k2N; j++) {
         const int m = (j + box / 2) / box;
         tv[j] = m == p ? 0ull - values[0] : values[m];
+    }
+    return 0;
+}
+
+int cufhe_amd_lvl2_test_vector_multi(const uint64_t* values, int p, int nout, uint64_t* tv)
+{
+    if (!values || !tv) return fail(-1, "null pointer");
+    if (nout != 1 && nout != 2 && nout != 4 && nout != 8) return fail(-1, "nout must be 1, 2, 4 or 8");
+    if (p < 2 || (p & (p - 1)) || p * nout > k2N / 2) return fail(-1, "p must be a power of two >= 2 with p nout <= N2/2");
+    // TV[nout q + j] = values[j][m], m the box of position nout q under cufhe_amd_lvl2_test_vector's boxes (the top half-box: -values[j][0])
+    const int box = k2N / p;
+    for (int q = 0; q < k2N / nout; q++) {
+        const int m = (nout * q + box / 2) / box;
+        for (int j = 0; j < nout; j++) {
+            const uint64_t* v = values + (size_t)j * p;
+            tv[nout * q + j] = m == p ? 0ull - v[0] : v[m];
+        }
     }
     return 0;
 }

@@ -451,7 +451,7 @@ int cufhe_amd_enqueue_gate(int device, void* stream, int op, int copying, cufhe_
     if (u2) {
         if (!out || !in0) return fail(-1, "null ciphertext");
         if (g_param_set >= 0 || g_lvl0_ring != 2048 || out->level != 0) return fail_lvl2_user_path();
-        if (!(u = lvl2_user_gate(op))) return fail_lvl2_user_op();
+        if (!(u = lvl2_user_gate(op))) return fail_lvl2_user_op(op);
     }
     if (!u && (op < 0 || op >= CUFHE_AMD_NUM_OPS)) return fail(-1, "unknown gate op");
     if (!out || !in0) return fail(-1, "null ciphertext");

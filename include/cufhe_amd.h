@@ -402,6 +402,8 @@ int cufhe_amd_polymul512_batch(int device, void* stream, size_t count, const int
  * internal streams (256 sixteen-bit ripple-carry adders, 32 carry levels of 256 gates behind one level of 8192: see DESIGN.md 2a).
  * Needs "sched_rename" (the recorded program is kept single-assignment); results, completion rules and tlwedevices do not change.
  * 0 = never, 2 = whenever a flush is eligible, whatever the cost model says (tests).
+ * "cb_rotations" (default 3): lvl02 rotations per circuit bootstrap -- 3 = one per TRGSW row with constant test vectors, 1 = all l rows
+ * from one multi-output rotation (see circuit bootstrapping below; other values -1).  Changing it waits for everything recorded.
  * "br_shape" (of the calling thread; default 0 = the launch-shape rules above): 1 / 2 / 3 put every blind rotation of the thread's
  * launches on the batch kernel / the paired low-latency kernel / the single one -- what the two lanes use, and tools/two_lane_probe.py.
  * "sched_level_gates" (default -1 = two grid rounds of the device, 16 gates per CU, while it has work -- on MI355X 4096: 32 768 gates through
@@ -468,12 +470,30 @@ int cufhe_amd_lvl2_keyswitch_batch(int device, void* stream, size_t count, const
  * Accepted, mixed freely with built-in ops: cufhe_amd_lvl2_gate_batch; and with "lvl0_ring" 2048 at level 0: cufhe_amd_gate,
  * _gate_batch, _gate_list, _enqueue_gate.  Refused with -1 before any device work: a lvl2 op on the default ring, at level 1 or with
  * "param_set" active; an id of the range without a definition; cufhe_amd_enqueue_gate_multi with a lvl2 op.
- * Not built: multi-output definitions (extraction at an index j inside both rotation kernels), a level-1 form (the ring has no lvl1
- * gates), tables that are themselves ciphertexts (the ring has no counterpart of cufhe_amd_lut_lookup_batch), and the circuit bootstrap
- * that takes all l TRGSW rows from one rotation. */
+ * Not built: a level-1 form (the ring has no lvl1 gates), tables that are themselves ciphertexts (the ring has no counterpart of
+ * cufhe_amd_lut_lookup_batch), cufhe_amd_enqueue_gate_multi and two-lane planning for the ring's multi-output definitions. */
 #define CUFHE_AMD_LVL2_USER_OP_BASE 8192
 #define CUFHE_AMD_LVL2_MAX_USER_GATES 64
 int cufhe_amd_lvl2_define_gate(const int32_t coeffs[3], uint32_t offset, const uint64_t* test_vector, int* op);
+/* Multi-output definitions of the ring: nout = 2^s in {2, 4, 8} functions of one x from ONE blind rotation.
+ * The modulus switch rounds to multiples of 2^s (nbit = 11):
+ *     abar_i = ((a_i + 2^(19+s)) >> (20+s)) << s,     bbar = 2 N2 - (((b + offset) >> (20+s)) << s)
+ * and the rotation leaves nout lvl2 TLWEs, output j = SampleExtract(j) of the accumulator (a, b):
+ *     out_j[m] = a[j - m] for m <= j,   out_j[m] = -a[N2 + j - m] for m > j,   out_j[N2] = b[j],
+ * each with a lvl20 key switch of its own.  The test vector interleaves the functions, TV[nout q + j] = f_j at position nout q
+ * (cufhe_amd_lvl2_test_vector_multi), and is required.  Every other rule is cufhe_amd_lvl2_define_gate's; a definition takes one of the
+ * 64 slots.  Output j of definition `op` is the op id CUFHE_AMD_LVL2_USER_OP_OUTPUT(op, j) = op + 64 j (ids 8192 .. 8703), an ordinary
+ * gate wherever lvl2 user gates are accepted; outputs of one definition on the same operand pointers in one call (one level's launch
+ * of the recorded API) share the rotation, in any order, and the words never depend on that.  Refused with -1 before any device work:
+ * an output id with j >= nout or on an undefined slot; nout outside {2, 4, 8}; a NULL test vector.  cufhe_amd_enqueue_gate_multi
+ * stays refused for ops of this ring.  cufhe_amd_lvl2_user_rotate_batch takes output 0's id (the one accumulator);
+ * cufhe_amd_lvl2_user_extract_batch takes any output id and writes that output alone (one rotation per call). */
+#define CUFHE_AMD_LVL2_USER_OP_OUTPUT(op, j) ((op) + (j) * CUFHE_AMD_LVL2_MAX_USER_GATES)
+int cufhe_amd_lvl2_define_gate_multi(const int32_t coeffs[3], uint32_t offset, int nout, const uint64_t* test_vector, int* op);
+/* Host helper: TV[nout q + j] = values[j][m], m the box of position nout q under cufhe_amd_lvl2_test_vector's boxes; the top half-box
+ * holds -values[j][0].  values: [nout][p] words; p and nout powers of two, p >= 2, nout <= 8, p nout <= N2/2; nout = 1 is
+ * cufhe_amd_lvl2_test_vector. */
+int cufhe_amd_lvl2_test_vector_multi(const uint64_t* values, int p, int nout, uint64_t* tv);
 /* Host helper: the boxes of cufhe_amd_test_vector on N2 = 2048 coefficients with 64-bit values: coefficient j in
  * [m N2/p - N2/(2p), m N2/p + N2/(2p)) holds values[m], the top half-box [N2 - N2/(2p), N2) holds -values[0].  p a power of two,
  * 2 <= p <= N2/2; lvl0 messages encoded as m -> m 2^32 / (2p).  values: p words, tv: N2 words. */
@@ -499,7 +519,13 @@ int cufhe_amd_lvl2_user_extract_batch(int device, void* stream, size_t count, in
  * K is the caller's private key-switching key, TFHEpp's layout [2][N2 + 1][t][2^basebit - 1][k+1][N] uint32 (2.35 GB):
  * K[u][i][j][v-1] = TRLWE_s1(v * k2_i * 2^(32 - (j+1) basebit) * f_u), k2_i = s2[i] (i < N2), k2_N2 = -1, f_0 = -s1(X), f_1 = 1.
  * Every word is deterministic (integer arithmetic only).  Needs cufhe_amd_lvl2_initialize (the lvl02 key) and cufhe_amd_cb_initialize;
- * default parameter set only ("param_set" active: -1). */
+ * default parameter set only ("param_set" active: -1).
+ * The one-rotation form, cufhe_amd_set_option("cb_rotations", 1) (3, the default: the above; anything else -1; switching synchronises
+ * first), takes all l rows of an input from ONE rotation: the rotation of a multi-output definition with
+ * s = 2 from the library's test vector TVcb[4 q + r] = 2^(63 - (r+1) Bgbit) for r < l, TVcb[4 q + 3] = 0, and
+ *   tlwe2_r = SampleExtract(r) of that accumulator, + mu_r on b (the same message bit * 2^(64 - (r+1) Bgbit)).
+ * Layout, private key switch, TRGSW2NTT, refusals and keys are unchanged; the option is honoured by cufhe_amd_cb_rotate_batch,
+ * cufhe_amd_circuit_bootstrap_batch and the recorded CUFHE_AMD_TL_CIRCUIT_BOOTSTRAP. */
 typedef struct cufhe_amd_cb_params {
     uint32_t n, N, k, l, Bgbit;        /* output TRGSW: lvl1, l = 3, Bgbit = 6 */
     uint32_t N2, l2, Bgbit2;           /* the lvl02 rotation */

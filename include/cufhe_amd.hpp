@@ -383,12 +383,29 @@ inline std::vector<uint32_t> TestVector(const std::vector<uint32_t>& values)
     return tv;
 }
 /// A user gate of the N = 2048 ring (cufhe_amd_lvl2_define_gate): define after lvl2::Initialize; tv: N2 = 2048 uint64 torus words
-/// (nullptr: the constant 2^61).  Apply / gApply take the handle on lvl0 ciphertexts while "lvl0_ring" is 2048; single output only.
-inline UserGate DefineGateLvl2(const std::array<int32_t, 3>& coeffs, uint32_t offset, const uint64_t* tv = nullptr)
+/// (nullptr: the constant 2^61).  Apply / gApply take the handle on lvl0 ciphertexts while "lvl0_ring" is 2048.  nout = 2, 4 or 8: a
+/// multi-output gate whose interleaved tv (TestVectorMultiLvl2) is required; output j is the single-output handle Output(g, j), and
+/// outputs recorded on the same operands that run in one launch share the rotation.
+inline UserGate DefineGateLvl2(const std::array<int32_t, 3>& coeffs, uint32_t offset, const uint64_t* tv = nullptr, int nout = 1)
 {
     UserGate g;
-    CUFHE_AMD_CHECK(cufhe_amd_lvl2_define_gate(coeffs.data(), offset, tv, &g.op));
+    if (nout == 1) CUFHE_AMD_CHECK(cufhe_amd_lvl2_define_gate(coeffs.data(), offset, tv, &g.op));
+    else CUFHE_AMD_CHECK(cufhe_amd_lvl2_define_gate_multi(coeffs.data(), offset, nout, tv, &g.op));
+    g.nout = nout;
     return g;
+}
+static_assert(CUFHE_AMD_LVL2_MAX_USER_GATES == CUFHE_AMD_MAX_USER_GATES, "UserGate::output serves both rings' id rules");
+/// output j of a multi-output gate as a single-output handle for Apply / gApply
+inline UserGate Output(UserGate g, int j) { return UserGate{g.output(j), 1}; }
+/// the interleaved 64-bit test vector of values.size() functions (1, 2, 4 or 8) on p messages each, p nout <= N2/2
+inline std::vector<uint64_t> TestVectorMultiLvl2(const std::vector<std::vector<uint64_t>>& values, int p)
+{
+    std::vector<uint64_t> flat;
+    for (const auto& v : values) flat.insert(flat.end(), v.begin(), v.begin() + std::min<size_t>(v.size(), (size_t)p));
+    if (flat.size() != values.size() * (size_t)p) CUFHE_AMD_CHECK(-1);
+    std::vector<uint64_t> tv(2048);
+    CUFHE_AMD_CHECK(cufhe_amd_lvl2_test_vector_multi(flat.data(), p, (int)values.size(), tv.data()));
+    return tv;
 }
 /// the 64-bit test vector of a function on values.size() lvl0 messages (a power of two, 2 .. N2/2) with a padding bit
 inline std::vector<uint64_t> TestVectorLvl2(const std::vector<uint64_t>& values)

@@ -1,8 +1,9 @@
-"""Circuit bootstrapping on the GPU (profiles/r09_circuit_bootstrapping.md).  One process:
-  - CB/s of cufhe_amd_circuit_bootstrap_batch (NTT-domain output) at 1, 8, 64, 512 and 4096 inputs: wall time per batch (median over
-    the repetitions, Synchronize around each) and its split into the lvl02 rotations / the private key switch from the library's
-    profiling events (cufhe_amd_profile_get: blind_rotate_ms = rotations, keyswitch_ms = private key switch), TRGSW2NTT and launch
-    gaps being the rest;
+"""Circuit bootstrapping on the GPU (profiles/r09_circuit_bootstrapping.md, profiles/r18_lvl2_multi_output.md).  One process:
+  - CB/s of cufhe_amd_circuit_bootstrap_batch (NTT-domain output) at 1, 8, 64, 512 and 4096 inputs, in BOTH forms -- three rotations
+    per input ("cb_rotations" 3, the default) and one ("cb_rotations" 1) -- alternated repetition by repetition in the same run: wall
+    time per batch (median over the repetitions, Synchronize around each) and its split into the lvl02 rotations / the private key
+    switch from the library's profiling events (cufhe_amd_profile_get: blind_rotate_ms = rotations, keyswitch_ms = private key
+    switch), TRGSW2NTT and launch gaps being the rest; then the ratio of the two forms' rates;
   - the latency of the 8 circuit bootstraps of one 8-bit address (the ROM read's selectors);
   - one 8-bit-address ROM read of a 256-entry ROM through the recorded per-gate API (address bits from the host, 8 circuit bootstraps,
     255 gCMUXNTT, the root fetched), ROM resident on the device, median of the repetitions; and the same read with the selectors
@@ -57,29 +58,42 @@ def main():
     pksk = np.random.default_rng(1).integers(0, 2**32, size=cb.PKS_KEY_WORDS, dtype=np.uint32)
     api.cb_initialize(pksk)
     rng = np.random.default_rng(3)
-    print("| inputs | ms / batch | CB/s | rotations ms | private KS ms | rest (TRGSW2NTT, gaps) ms | private KS share |")
-    print("|---:|---:|---:|---:|---:|---:|---:|")
+    print("| inputs | rotations per input | ms / batch | CB/s | rotations ms | private KS ms | rest (TRGSW2NTT, gaps) ms | private KS share |")
+    print("|---:|---:|---:|---:|---:|---:|---:|---:|")
+    ratios = []
     for count in (1, 8, 64, 512, 4096):
         tl = keys.encrypt(rng.integers(0, 2, size=count).astype(np.uint8), 0, seed=count)
         d0 = api.DeviceBuffer(tl.size).upload(tl)
         dn = api.DeviceBuffer(count * cb.TRGSW_WORDS * 2)
-        api.circuit_bootstrap_batch(d0, count, trgsw_ntt=dn)
-        eng.Synchronize()
-        wall, br, ks = [], [], []
-        for _ in range(reps):
-            api.profile_enable(True)
-            api.profile_get(reset=True)
-            t0 = time.perf_counter()
+        forms = (3, 1)
+        for f in forms:                     # warm both forms (the half-wave key layout, the library's test-vector row)
+            api.set_option("cb_rotations", f)
             api.circuit_bootstrap_batch(d0, count, trgsw_ntt=dn)
-            eng.Synchronize()
-            wall.append((time.perf_counter() - t0) * 1e3)
-            p = api.profile_get(reset=True)
-            api.profile_enable(False)
-            br.append(p.blind_rotate_ms)
-            ks.append(p.keyswitch_ms)
-        w, b, k = statistics.median(wall), statistics.median(br), statistics.median(ks)
-        print(f"| {count} | {w:.3f} | {count / w * 1e3:.0f} | {b:.3f} | {k:.3f} | {w - b - k:.3f} | {100 * k / w:.1f} % |")
+        eng.Synchronize()
+        wall, br, ks = {f: [] for f in forms}, {f: [] for f in forms}, {f: [] for f in forms}
+        for _ in range(reps):
+            for f in forms:                 # alternated: both forms see the same clocks and the same neighbours
+                api.set_option("cb_rotations", f)
+                api.profile_enable(True)
+                api.profile_get(reset=True)
+                t0 = time.perf_counter()
+                api.circuit_bootstrap_batch(d0, count, trgsw_ntt=dn)
+                eng.Synchronize()
+                wall[f].append((time.perf_counter() - t0) * 1e3)
+                p = api.profile_get(reset=True)
+                api.profile_enable(False)
+                br[f].append(p.blind_rotate_ms)
+                ks[f].append(p.keyswitch_ms)
+        api.set_option("cb_rotations", 3)
+        med = {}
+        for f in forms:
+            w, b, k = statistics.median(wall[f]), statistics.median(br[f]), statistics.median(ks[f])
+            med[f] = w
+            print(f"| {count} | {f} | {w:.3f} | {count / w * 1e3:.0f} | {b:.3f} | {k:.3f} | {w - b - k:.3f} | {100 * k / w:.1f} % |")
+        ratios.append((count, med[3] / med[1]))
         del d0, dn
+    print()
+    print("one rotation against three, CB/s ratio: " + ", ".join(f"{c} inputs {r:.2f}x" for c, r in ratios))
 
     # the selectors of one 8-bit address
     tl = keys.encrypt(rng.integers(0, 2, size=8).astype(np.uint8), 0, seed=99)
