@@ -64,7 +64,8 @@ struct PinnedBlock { void* host = nullptr; size_t bytes = 0; hipEvent_t done = n
 // Per-stream device workspace (temporaries + descriptor arrays of one launch sequence).
 // Work on one stream is ordered, so the next sequence on the same stream may overwrite the
 // workspace of the previous one; distinct streams get distinct workspaces.  Grow-only.
-struct Workspace { char* base = nullptr; size_t bytes = 0; };
+// ks_digits: the digit words of the stream's last matrix-product key switch (launch_keyswitch), grow-only like the rest.
+struct Workspace { char* base = nullptr; size_t bytes = 0; char* ks_digits = nullptr; size_t ks_digit_bytes = 0; };
 
 struct DeviceState {
     bool ntt_ready = false, keys_ready = false;
@@ -74,6 +75,7 @@ struct DeviceState {
     Ntt512Tables* tables512 = nullptr;   // [3]: the two 512-point halves (low-latency kernel), stand-alone N = 512
     double* bk_ntt = nullptr;
     uint32_t* ksk = nullptr;
+    ksmm_v4i* ksk_mm = nullptr;          // the same key in matrix form [j][column][16] int8 (keyswitch_mm_kernel); null: could not be allocated
     uint32_t* tvs = nullptr;             // [kMaxUserGates][kN]: the user gates' test vectors (cufhe_amd_define_gate); CleanUp frees it
     // device fault word: pinned, host-coherent, mapped into the device (kernels_common.hip.h: kFault*); sticky until CleanUp
     uint32_t* fault_host = nullptr;
@@ -437,11 +439,40 @@ void launch_keyswitch_direct(hipStream_t st, const typename S::Desc* d, size_t c
     if (SPLIT > 1) hipLaunchKernelGGL(keyswitch_zero_kernel<S>, dim3((unsigned)count), dim3(256), 0, st, d, (int)count);
     hipLaunchKernelGGL((keyswitch_direct_kernel<S, SPLIT>), dim3((unsigned)count * SPLIT), dim3(kKsThreads), 0, st, d, (int)count, ksk_padded);
 }
+// keyswitch_mm_kernel: the digit words of the launch into the stream's grow-only buffer, then the product (kernels_ks2.hip.h)
+int launch_keyswitch_matrix(DeviceState& s, hipStream_t st, const LinDesc* d, size_t count)
+{
+    uint32_t* dig = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(s.staging_mu);
+        Workspace& w = s.workspaces[st];
+        const size_t bytes = ks_mm_digit_bytes(count);
+        if (w.ks_digit_bytes < bytes) {
+            if (w.ks_digits) {
+                HIP_TRY(hipStreamSynchronize(st));
+                HIP_TRY(hipFree(w.ks_digits));
+                w.ks_digits = nullptr; w.ks_digit_bytes = 0;
+            }
+            HIP_TRY(hipMalloc((void**)&w.ks_digits, bytes));
+            w.ks_digit_bytes = bytes;
+        }
+        dig = (uint32_t*)w.ks_digits;
+    }
+    const unsigned tiles = (unsigned)((count + kKsMmRows - 1) / kKsMmRows);
+    hipLaunchKernelGGL(ks_mm_digits_kernel<KsShapeDefault>, dim3(tiles, kKsMmSteps / kKsMmDigitChunk), dim3(256), 0, st, d, (int)count, dig);
+    hipLaunchKernelGGL(keyswitch_mm_kernel<KsShapeDefault>, dim3(tiles * kKsMmWordBlocks), dim3(64), 0, st, d, (int)count, s.ksk_mm, dig);
+    return 0;
+}
 int launch_keyswitch(DeviceState& s, hipStream_t st, const LinDesc* d, size_t count)
 {
     if (count == 0) return 0;
     ProfScope prof{s, st, count, true};
     if (int rc = prof.begin()) return rc;
+    if (s.ksk_mm && plan::use_matrix_keyswitch(count, cus_of(s), g_tuning)) {
+        if (int rc = launch_keyswitch_matrix(s, st, d, count)) return rc;
+        HIP_TRY(hipGetLastError());
+        return prof.commit();
+    }
     const plan::KsPlan p = plan_keyswitch_of<KsShapeDefault>(s, count, plan::kKsDefaultPath);
     if (p.kernel == plan::KsKernel::Split8) {
         launch_keyswitch_direct<KsShapeDefault, kKsSplit>(st, d, count, s.ksk);
@@ -1061,6 +1092,17 @@ int upload_ksk_padded(DevPtr<uint32_t>& d, const uint32_t* ksk, size_t rows, siz
                         hipMemcpyHostToDevice));
     return 0;
 }
+// The padded key in matrix form for keyswitch_mm_kernel (42 MB more per device).  A device without room for it keeps the other
+// kernels at every count: *out stays null and that is no error.
+void build_ksk_matrix(const uint32_t* ksk_padded, ksmm_v4i** out)
+{
+    *out = nullptr;
+    ksmm_v4i* p = nullptr;
+    if (hipMalloc((void**)&p, kKsMmKeyBytes) != hipSuccess) { (void)hipGetLastError(); return; }
+    hipLaunchKernelGGL(ks_mm_key_kernel, dim3(KsShapeDefault::kn, kKsMmColumns / 256), dim3(256), 0, 0, ksk_padded, p);
+    if (hipGetLastError() != hipSuccess) { (void)hipFree(p); return; }
+    *out = p;
+}
 
 }  // namespace
 
@@ -1171,7 +1213,7 @@ int cufhe_amd_initialize(const uint32_t* bk, size_t bk_words, const uint32_t* ks
     if (bk_words != want_bk) return fail(-1, "bootstrapping key has the wrong size for this parameter set");
     if (ksk_words != want_ksk) return fail(-1, "key-switching key has the wrong size for this parameter set");
     // Build first, swap last: the new keys of EVERY device are allocated and converted beside whatever is loaded; only when all of that
-    // has succeeded do they replace the old ones.  A failure on the way (a full device: 104 MB per replica) frees what this call
+    // has succeeded do they replace the old ones.  A failure on the way (a full device: 104 MB per replica, and 42 MB for the key switch's matrix form, which may be missing) frees what this call
     // allocated and leaves every device with the keys -- and the results -- it had.
     struct Built { DevPtr<double> bk_ntt; DevPtr<uint32_t> ksk, d_bk; };
     std::vector<Built> built((size_t)g_gpu_num);      // the torus-domain staging copies d_bk are freed on every return
@@ -1196,8 +1238,12 @@ int cufhe_amd_initialize(const uint32_t* bk, size_t bk_words, const uint32_t* ks
         DeviceState& s = g_dev[i];
         (void)hipSetDevice(phys_device(i));
         if (s.keys_ready) { (void)hipFree(s.bk_ntt); (void)hipFree(s.ksk); }
+        if (s.ksk_mm) { (void)hipFree(s.ksk_mm); s.ksk_mm = nullptr; }
         s.bk_ntt = built[(size_t)i].bk_ntt.release();
         s.ksk = built[(size_t)i].ksk.release();
+        // the matrix form is optional (a device without 42 MB to spare keeps the other key-switch kernels), so it cannot fail the swap
+        build_ksk_matrix(s.ksk, &s.ksk_mm);
+        if (hipDeviceSynchronize() != hipSuccess) { (void)hipGetLastError(); if (s.ksk_mm) (void)hipFree(s.ksk_mm); s.ksk_mm = nullptr; }
         s.keys_ready = true;
     }
     return 0;
@@ -1220,6 +1266,7 @@ int cufhe_amd_cleanup(void)
             v->clear();
         }
         if (s.keys_ready) { HIP_TRY(hipFree(s.bk_ntt)); HIP_TRY(hipFree(s.ksk)); }
+        if (s.ksk_mm) { HIP_TRY(hipFree(s.ksk_mm)); s.ksk_mm = nullptr; }
         if (s.tvs) { HIP_TRY(hipFree(s.tvs)); s.tvs = nullptr; }
         if (s.tvs2) { HIP_TRY(hipFree(s.tvs2)); s.tvs2 = nullptr; }
         ps_release(i);
@@ -1234,7 +1281,7 @@ int cufhe_amd_cleanup(void)
         if (s.fault_host) { (void)hipHostFree(s.fault_host); s.fault_host = nullptr; s.fault = nullptr; }   // the fault, if any, ends with the keys
         for (auto& b : s.staging) { (void)hipEventDestroy(b.done); (void)hipHostFree(b.host); }
         s.staging.clear();
-        for (auto& kv : s.workspaces) (void)hipFree(kv.second.base);
+        for (auto& kv : s.workspaces) { (void)hipFree(kv.second.base); (void)hipFree(kv.second.ks_digits); }
         s.workspaces.clear();
         s.ntt_ready = s.keys_ready = false;
         s.br_lds_opt_in = s.ks_lds_opt_in = false;
@@ -1279,6 +1326,7 @@ int cufhe_amd_stream_destroy(int device, void* stream)
         if (it != s.workspaces.end()) {
             HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
             (void)hipFree(it->second.base);
+            (void)hipFree(it->second.ks_digits);
             s.workspaces.erase(it);
         }
     }
@@ -1837,6 +1885,11 @@ int cufhe_amd_set_option(const char* key, long value)
     if (!strcmp(key, "ks_per_wg")) {
         if (value != -1 && (value < 1 || value > 16)) return fail(-1, "ks_per_wg must be -1 or 1..16");
         g_tuning.ks_per_wg = value;
+        return 0;
+    }
+    if (!strcmp(key, "ks_mm_threshold")) {
+        if (value < -1) return fail(-1, "ks_mm_threshold must be -1 (the measured rule), 0 (never) or a count of ciphertexts");
+        g_tuning.ks_mm_threshold = value;
         return 0;
     }
     if (!strcmp(key, "lvl2_kernel")) {

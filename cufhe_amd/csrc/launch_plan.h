@@ -35,6 +35,7 @@ struct Tuning {
     // 4096: 192 against 223)
     long lvl2_kernel = -1;
     long pack_slices = -1;         // TLWE packing: slices of i per tile of inputs (plan_pack); -1 by the rule, else clamped to 1 .. max
+    long ks_mm_threshold = -1;     // lvl10 key switches per launch from which the matrix-product kernel runs: -1 by the measured rule, 0 never
 };
 
 // ---- blind rotation (kN = 1024, the default path) ----
@@ -212,6 +213,21 @@ inline KsPlan plan_keyswitch(size_t count, int cus, int kn, int min_slices, KsRu
     }
     if (p.kernel == KsKernel::Shared) ks_shared_shape(count, cus, kn, min_slices, t, &p.per_wg, &p.slices);
     return p;
+}
+
+// The lvl10 key switch as an int8 matrix product (keyswitch_mm_kernel, kernels_ks2.hip.h) instead of the plan above?  Only when none
+// of the four options that force a shape of the other kernels is set, so that every test and tool that asks for one of them gets it.
+// plan_keyswitch and the cost models above do not know this kernel: the two-lane scheduler prices large key switches as before.
+// The measured rule, in ciphertexts per CU (MI355X, ms per launch, tools/ks_mm_times.py, profiles/r19_keyswitch_matrix.md):
+//   the plan above   0.104 (256)  0.173 (512)  0.305 (1024)  0.455 (1536)  0.549 (2048)  0.824 (3072)  1.048 (4096)
+//   matrix product   0.139 (256)  0.141 (512)  0.143 (1024)  0.143 (1536)  0.145 (2048)  0.160 (3072)  0.216 (4096)
+// so: from two ciphertexts per CU on.
+constexpr long kKsMmFromPerCu = 2;
+inline bool use_matrix_keyswitch(size_t count, int cus, const Tuning& t)
+{
+    if (t.ks_split_threshold != -1 || t.ks_wg_threshold != -1 || t.ks_per_wg != -1 || t.ks_slices != -1) return false;
+    const long from = t.ks_mm_threshold < 0 ? kKsMmFromPerCu * (long)device_cus(cus) : t.ks_mm_threshold;
+    return from > 0 && (long)count >= from;
 }
 
 // ---- the smaller rules ----

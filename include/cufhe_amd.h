@@ -359,6 +359,10 @@ int cufhe_amd_polymul512_batch(int device, void* stream, size_t count, const int
  * the measured times: 0.07 ms for 64, 0.12 for 256, 0.31 for 1024, 0.57 for 2048, 0.86 for 3072, 1.04 ms for 4096.
  * "ks_wg_threshold" (default -1 = never) forces one workgroup per ciphertext up to the given count (0.22 ms up to 256,
  * 0.8 ms at 1024).  All variants produce identical words.
+ * "ks_mm_threshold": ciphertexts per launch from which the lvl10 key switch runs as an exact int8 matrix product on the
+ * matrix cores (keyswitch_mm_kernel; the key is kept a second time in matrix form, 42 MB per device): -1 (default) = the
+ * measured rule, 0 = never, n > 0 = from n ciphertexts on.  It applies only while the four "ks_*" options above are at -1,
+ * and not to the N = 2048 ring or the parameter sets.  The same words as every other variant.
  * "ps_batch_threshold" (default -1 = by cost: 1025, 1281 for N = 512, 1537 for sets with key limbs): rotations per launch from which the parameter-set path
  * (cufhe_amd_ps_*) uses the wave-per-rotation kernel instead of a workgroup per rotation.
  * "lvl0_ring": 1024 (default) or 2048 -- the ring through which gates on lvl0 ciphertexts
