@@ -836,6 +836,63 @@ def ps_trlwe_op_batch(ps, op, out, inp, count, device=0, stream=None):
     check(lib.cufhe_amd_ps_trlwe_op_batch(int(ps), device, stream, int(op), count, out.ptr, inp.ptr))
 
 
+# ---- user gates on a parameter set (cufhe_amd_ps_define_gate, include/cufhe_amd.h) ----
+PS_USER_OP_BASE, PS_MAX_USER_GATES = 12288, 64
+
+
+def ps_user_op_output(op, j):
+    """the op id of output j of a set's multi-output definition `op` (CUFHE_AMD_PS_USER_OP_OUTPUT)"""
+    return op + j * PS_MAX_USER_GATES
+
+
+def ps_define_gate(ps, coeffs, offset=0, test_vector=None, nout=1):
+    """A user gate of compiled parameter set `ps`: x = c0 in0 + c1 in1 + c2 in2 + (0, .., 0, offset) on the set's ciphertexts,
+    bootstrapped through `test_vector` (N torus words of the set; None: the constant mu).  Returns the op id: an op of ps_gate_batch on
+    that set at either level, and of gate_batch / Apply / gApply while "param_set" is that set.  nout = 2, 4 or 8: a multi-output
+    definition (interleaved test vector of ps_test_vector_multi, required); output j is the op ps_user_op_output(op, j)."""
+    c = np.zeros(3, dtype=np.int32)
+    c[:len(coeffs)] = coeffs
+    tv = None
+    if test_vector is not None:
+        tv = np.ascontiguousarray(test_vector, dtype=np.uint32)
+        if tv.size != ps_params(ps).N:
+            raise ValueError(f"test vector must have N = {ps_params(ps).N} words")
+    op = ctypes.c_int()
+    if nout != 1:
+        check(lib.cufhe_amd_ps_define_gate_multi(int(ps), c.ctypes.data_as(_lib.c_i32p), int(offset) & 0xFFFFFFFF, int(nout),
+                                                 _ptr(tv) if tv is not None else None, ctypes.byref(op)))
+        return op.value
+    check(lib.cufhe_amd_ps_define_gate(int(ps), c.ctypes.data_as(_lib.c_i32p), int(offset) & 0xFFFFFFFF, _ptr(tv) if tv is not None else None,
+                                       ctypes.byref(op)))
+    return op.value
+
+
+def ps_test_vector(ps, values):
+    """The test vector (N words of set `ps`) of a function on len(values) messages (a power of two, 2 .. N/2) encoded with a padding
+    bit, m -> m 2^32 / (2p): values are the output torus words (cufhe_amd_ps_test_vector; host only)."""
+    v = np.ascontiguousarray(values, dtype=np.uint32)
+    tv = np.empty(ps_params(ps).N, dtype=np.uint32)
+    check(lib.cufhe_amd_ps_test_vector(int(ps), _ptr(v), int(v.size), _ptr(tv)))
+    return tv
+
+
+def ps_test_vector_multi(ps, values):
+    """The interleaved test vector of nout = len(values) functions (1, 2, 4 or 8) on p = len(values[0]) messages each, p nout <= N/2
+    of set `ps` (cufhe_amd_ps_test_vector_multi; host only)."""
+    v = np.ascontiguousarray(values, dtype=np.uint32)
+    if v.ndim != 2:
+        raise ValueError("values must be [nout][p]")
+    tv = np.empty(ps_params(ps).N, dtype=np.uint32)
+    check(lib.cufhe_amd_ps_test_vector_multi(int(ps), _ptr(v), int(v.shape[1]), int(v.shape[0]), _ptr(tv)))
+    return tv
+
+
+def ps_user_rotate(ps, op, in0, acc, count, in1=None, in2=None, steps=-1, device=0, stream=None):
+    """acc[count][(k+1) N]: the accumulators of the set's user gate `op` on lvl0 operands after `steps` CMux steps (parity hook)."""
+    check(lib.cufhe_amd_ps_user_rotate(int(ps), device, stream, count, int(op), in0.ptr, in1.ptr if in1 is not None else None,
+                                       in2.ptr if in2 is not None else None, acc.ptr, steps))
+
+
 def ps_trgsw_to_ntt_batch(ps, trgsw, trgsw_ntt, count, device=0, stream=None):
     """TRGSW2NTT on a set: trgsw[count][(k+1)l][k+1][N] torus words -> trgsw_ntt[count][limbs][(k+1)l][k+1][N] doubles (2 words each)"""
     check(lib.cufhe_amd_ps_trgsw_to_ntt_batch(int(ps), device, stream, count, trgsw.ptr, trgsw_ntt.ptr))

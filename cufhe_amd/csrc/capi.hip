@@ -559,6 +559,49 @@ int fail_lvl2_user_path()
                     "not with \"param_set\" active");
 }
 
+// User gates of the compiled parameter sets (cufhe_amd_ps_define_gate, _define_gate_multi, paramsets.inc.h): one table of definitions
+// for all sets, in an id range of its own, each definition made for ONE set (g_ps_user_set[k]); its test vector (N words of that set) is
+// row k of that set's PsState::tvs on every device.  Same write-once discipline as g_user; output j of a multi-output definition k is
+// CUFHE_AMD_PS_USER_OP_OUTPUT(base + k, j) = base + k + j * CUFHE_AMD_PS_MAX_USER_GATES.  The ids of cufhe_amd_define_gate and
+// cufhe_amd_lvl2_define_gate keep their meaning: they stay refused on a set.
+static_assert(CUFHE_AMD_PS_MAX_USER_GATES == kMaxUserGates, "the header's capacity is the device tables'");
+static_assert(CUFHE_AMD_PS_USER_OP_BASE > CUFHE_AMD_TL_CMUX_ROTATE(2 * kN - 1) &&
+                  CUFHE_AMD_PS_USER_OP_BASE >= CUFHE_AMD_LVL2_USER_OP_BASE + (kMaxUserGates2 << kMaxOutputShift) &&
+                  CUFHE_AMD_PS_USER_OP_BASE >= CUFHE_AMD_USER_OP_BASE + (kMaxUserGates << kMaxOutputShift) &&
+                  CUFHE_AMD_PS_USER_OP_BASE > CUFHE_AMD_TL_SEIKS_AT(kN - 1) && CUFHE_AMD_PS_USER_OP_BASE > CUFHE_AMD_TL_CIRCUIT_BOOTSTRAP,
+              "parameter-set user op ids lie above every other id range");
+static_assert(CUFHE_AMD_PS_USER_OP_OUTPUT(CUFHE_AMD_PS_USER_OP_BASE + kMaxUserGates - 1, (1 << kMaxOutputShift) - 1) ==
+                  CUFHE_AMD_PS_USER_OP_BASE + (kMaxUserGates << kMaxOutputShift) - 1, "parameter-set output ids fill [base, base + 8 * 64)");
+UserGate g_ps_user[kMaxUserGates];
+int g_ps_user_set[kMaxUserGates];
+std::atomic<int> g_ps_user_count{0};
+bool is_ps_user_op(int op) { return op >= CUFHE_AMD_PS_USER_OP_BASE && op < CUFHE_AMD_PS_USER_OP_BASE + (kMaxUserGates << kMaxOutputShift); }
+int ps_user_def(int op) { return (op - CUFHE_AMD_PS_USER_OP_BASE) % kMaxUserGates; }      // definition index k of a set's user op id
+int ps_user_output(int op) { return (op - CUFHE_AMD_PS_USER_OP_BASE) / kMaxUserGates; }   // output j of a set's user op id
+// the definition of `op` made for parameter set `set`; nullptr when op is not a defined user gate of that set or names an output
+// j >= nout of one
+const UserGate* ps_user_gate(int op, int set)
+{
+    if (!is_ps_user_op(op) || set < 0) return nullptr;
+    const int k = ps_user_def(op);
+    if (k >= g_ps_user_count.load(std::memory_order_acquire) || g_ps_user_set[k] != set) return nullptr;
+    return ps_user_output(op) < g_ps_user[k].nout ? &g_ps_user[k] : nullptr;
+}
+// the refusal of an id of the range that is no defined user gate of parameter set `set`
+int fail_ps_user_op(int op, int set)
+{
+    const int k = ps_user_def(op);
+    if (k >= g_ps_user_count.load(std::memory_order_acquire))
+        return fail(-1, "parameter set user gate op not defined (cufhe_amd_ps_define_gate; CleanUp drops the definitions)");
+    if (g_ps_user_set[k] != set) return fail(-1, "user gate op was defined for another parameter set (cufhe_amd_ps_define_gate(set, ...))");
+    return fail(-1, "unknown gate op: not an output of a defined multi-output user gate of this parameter set (CUFHE_AMD_PS_USER_OP_OUTPUT(op, j), j < nout)");
+}
+int fail_ps_user_path()
+{
+    return fail(-1, "user gates of a parameter set run on that set only: through cufhe_amd_ps_gate_batch or with \"param_set\" active, "
+                    "not on the default path or on the N = 2048 ring");
+}
+
 int user_def(int op) { return (op - CUFHE_AMD_USER_OP_BASE) % kMaxUserGates; }      // definition index k of a user op id
 int user_output(int op) { return (op - CUFHE_AMD_USER_OP_BASE) / kMaxUserGates; }   // output j of a user op id
 // the definition of `op`; nullptr when op is not a defined user gate or names an output j >= nout of one
@@ -606,9 +649,11 @@ long g_param_set = -1;
 //   ks_mu              the mu of the Mux sum in the key switch
 //   lvl1_gates         whether it has gates on Mid ciphertexts (level 1)
 //   s, ready(), rotate(), keyswitch()   its device, the readiness check and the two launchers
-//   user_gates         whether its rotation kernels read LinDesc::pad as a test-vector row (user gates; the default path only)
+//   user_gates         whether its rotation kernels read LinDesc::pad as a test-vector row (user gates: the default path with the ids of
+//                      cufhe_amd_define_gate, a parameter set with those of cufhe_amd_ps_define_gate made for it)
+//   set_index          the compiled parameter set the path runs on, -1 for the default path and the N = 2048 ring
 //   lvl2_user_gates    whether it runs the lvl2 user gates (RotDesc2::pad = make_pad2(row, s); the N = 2048 ring only); then rotate() takes
-//                      one more argument: whether any descriptor names a row
+//                      one more argument: whether any descriptor names a row (so does a parameter set's: set_index >= 0)
 //   user_op(op), tv_pad(op, u)   the path's own definition lookup (nullptr: not a defined user gate of this path) and pad rule
 //   user_def(op), user_output(op), multi_pad(op, u)   definition index and output j of a user op id of the path, and the pad of a
 //                      multi-output definition's rotation (row and output shift)
@@ -618,10 +663,16 @@ template <class P, class GetGate>
 int lower_gates(const P& p, hipStream_t st, int level, size_t count, GetGate get)
 {
     using Mid = typename P::Mid;
-    if constexpr (!P::user_gates) {
+    if constexpr (!P::user_gates || P::set_index >= 0) {
         for (size_t g = 0; g < count; g++)
             if (is_user_op(get(g).op))
                 return fail(-1, "user gates run on the default path only: not with \"param_set\" active or on the N = 2048 ring (\"lvl0_ring\")");
+    }
+    for (size_t g = 0; g < count; g++) {      // a set's user gates: on that set only
+        const int op = get(g).op;
+        if (!is_ps_user_op(op)) continue;
+        if (P::set_index < 0) return fail_ps_user_path();
+        if (!ps_user_gate(op, P::set_index)) return fail_ps_user_op(op, P::set_index);
     }
     if constexpr (!P::lvl2_user_gates) {
         for (size_t g = 0; g < count; g++)
@@ -638,7 +689,7 @@ int lower_gates(const P& p, hipStream_t st, int level, size_t count, GetGate get
     if (level != 0 && level != 1) return fail(-1, "level must be 0 or 1");
     if (count == 0) return 0;
     const uint32_t negmu = 0u - kMu;
-    bool tv_rows = false;         // a rotation descriptor names a test-vector row (read by the lvl2 path's launcher only)
+    bool tv_rows = false;         // a rotation descriptor names a test-vector row (read by the launchers of the lvl2 path and of the sets)
 
     // Outputs of one multi-output definition on the same operands form one evaluation (one rotation, all nout outputs extracted into
     // scratch): fused by (definition, in0, in1, in2) whatever the order of the list.  fuse[g] is the evaluation of gate g.
@@ -653,7 +704,7 @@ int lower_gates(const P& p, hipStream_t st, int level, size_t count, GetGate get
         const int op = get(g).op;
         if constexpr (P::user_gates || P::lvl2_user_gates) {
             const UserGate* u = P::user_op(op);
-            if (P::user_gates && is_user_op(op) && !u) return fail_user_op(op);
+            if (P::user_gates && P::set_index < 0 && is_user_op(op) && !u) return fail_user_op(op);
             if (u) {
                 if (u->nout > 1) {
                     const GateRef gr = get(g);
@@ -828,7 +879,7 @@ int lower_gates(const P& p, hipStream_t st, int level, size_t count, GetGate get
     if (int rc = upload_descs(p.s, sc, pre, &dpre)) return rc;
     if (int rc = launch_lincomb(st, dpre, pre.size(), (int)level_words)) return rc;
     if (level == 0) {
-        if constexpr (P::lvl2_user_gates) {
+        if constexpr (P::lvl2_user_gates || P::set_index >= 0) {
             if (int rc = p.rotate(st, drot, rot.size(), P::n, nullptr, tv_rows)) return rc;
         } else {
             if (int rc = p.rotate(st, drot, rot.size(), P::n, nullptr)) return rc;
@@ -836,7 +887,11 @@ int lower_gates(const P& p, hipStream_t st, int level, size_t count, GetGate get
         if (int rc = p.keyswitch(st, dks, ks.size())) return rc;
     } else if constexpr (P::lvl1_gates) {
         if (int rc = p.keyswitch(st, dks, ks.size())) return rc;
-        if (int rc = p.rotate(st, drot, rot.size(), P::n, nullptr)) return rc;
+        if constexpr (P::set_index >= 0) {
+            if (int rc = p.rotate(st, drot, rot.size(), P::n, nullptr, tv_rows)) return rc;
+        } else {
+            if (int rc = p.rotate(st, drot, rot.size(), P::n, nullptr)) return rc;
+        }
     }
     return launch_lincomb(st, dlin, lin.size(), level ? P::mid_words : P::lvl0_words);
 }
@@ -979,6 +1034,7 @@ struct BasePath {
     static constexpr int lvl0_words = kLvl0Words, mid_words = kLvl1Words, n = kLvl0N;
     static constexpr uint32_t ks_mu = kMu;
     static constexpr bool lvl1_gates = true, has_cmux = true, user_gates = true, packed_rom = true, lvl2_user_gates = false;
+    static constexpr int set_index = -1;
     static const UserGate* user_op(int op) { return user_gate(op); }
     static int user_def(int op) { return ::user_def(op); }
     static int user_output(int op) { return ::user_output(op); }
@@ -1020,6 +1076,13 @@ int run_gates(int device, void* stream, int level, size_t count, GetGate get)
         if (!is_lvl2_user_op(op)) continue;
         if (g_param_set >= 0 || level != 0 || g_lvl0_ring != 2048) return fail_lvl2_user_path();
         if (!lvl2_user_gate(op)) return fail_lvl2_user_op(op);
+    }
+    // a parameter set's user ops: only while the gates run on the set they were defined for
+    for (size_t g = 0; g < count; g++) {
+        const int op = get(g).op;
+        if (!is_ps_user_op(op)) continue;
+        if (g_param_set < 0 || (level == 0 && g_lvl0_ring == 2048)) return fail_ps_user_path();
+        if (!ps_user_gate(op, (int)g_param_set)) return fail_ps_user_op(op, (int)g_param_set);
     }
     if (level == 0 && g_lvl0_ring == 2048) return run_gates_lvl2(device, stream, count, get);
     if ((level == 0 || level == 1) && g_param_set >= 0) return run_gates_ps((int)g_param_set, device, stream, level, count, get);
@@ -1291,6 +1354,7 @@ int cufhe_amd_cleanup(void)
     lvl2_release_host_key();
     g_user_count.store(0, std::memory_order_release);
     g_user2_count.store(0, std::memory_order_release);
+    g_ps_user_count.store(0, std::memory_order_release);
     return 0;
 }
 

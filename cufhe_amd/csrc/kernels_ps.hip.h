@@ -137,6 +137,32 @@ __host__ __device__ constexpr uint32_t ps_decomp_signmask()
     return m;
 }
 
+// ---- user gates on a set (cufhe_amd_ps_define_gate): the helpers of kernels_common.hip.h over the set's ring ----------------
+// The set's table `tvs` is [kMaxUserGates][N] torus words; LinDesc::pad = 0 is the constant mu, else row (pad & 0xff) - 1 and the
+// output shift s = pad >> 8 (make_pad).  Coefficient e of X^bbar TV in Z[X]/(X^N + 1), 1 <= bbar <= 2N:
+template <class PS>
+__device__ __forceinline__ uint32_t ps_rotated_tv_coef(const uint32_t* __restrict__ tv, uint32_t bbar, uint32_t e)
+{
+    constexpr uint32_t N = 1u << PS::Nbit;
+    const uint32_t k = (e - bbar) & (2 * N - 1);
+    const uint32_t v = tv[k & (N - 1)];
+    return k >= N ? 0u - v : v;
+}
+template <class PS>
+__device__ __forceinline__ const uint32_t* ps_desc_tv(const uint32_t* __restrict__ tvs, uint32_t pad)
+{
+    return tvs + (size_t)((pad & 0xffu) - 1) * (1u << PS::Nbit);
+}
+// the modulus switch rounded to multiples of 2^s (ms_abar / ms_bbar with the set's Nbit; s = 0 is the gates' own).  abar is kept
+// mod 2N: the rotation kernels read bit Nbit of it as the sign of X^abar
+template <class PS>
+__device__ __forceinline__ uint32_t ps_ms_abar(uint32_t a, int s)
+{
+    return (((a + (1u << (32 - 2 - PS::Nbit + s))) >> (32 - 1 - PS::Nbit + s)) << s) & ((2u << PS::Nbit) - 1);
+}
+template <class PS>
+__device__ __forceinline__ uint32_t ps_ms_bbar(uint32_t b, int s) { return (2u << PS::Nbit) - ((b >> (32 - 1 - PS::Nbit + s)) << s); }
+
 // ---- one polynomial per wave, either ring size ------------------------------------------------
 template <int NBIT> struct Poly;
 template <> struct Poly<10> {
@@ -308,11 +334,16 @@ __global__ __launch_bounds__(kNttThreads) void bk_to_ntt_ps_kernel(
 // descs: in0/in1 lvl0 TLWEs (n + 1 words), out a lvl1 TLWE (k N + 1 words) or null; acc_dump (optional)
 // receives the raw accumulator ((k+1) N words).  include/gatebootstrapping_gpu.cuh:29-52,115-345,
 // src/bootstrap_gpu.cu:366-381.
+// TV (both rotation kernels): the instantiation that also reads LinDesc::pad.  A descriptor with pad != 0 (a user gate of the set)
+// starts from row (pad & 0xff) - 1 of `tvs` instead of mu and, with s = pad >> 8 > 0, switches the modulus to multiples of 2^s and
+// writes 2^s contiguous lvl1 TLWEs, output j extracted at index j.  The <false> instantiations ignore pad and `tvs`: they are the
+// kernels every launch without a user gate runs, instruction for instruction what they were before the sets had user gates (with
+// the branches compiled in, 4096 NAND took 0.2 to 1.3 % longer: profiles/r20_ps_user_gates.md).
 // ----------------------------------------------------------------------------------------------
-template <class PS>
+template <class PS, bool TV>
 __global__ __launch_bounds__(64 * kPsWavesOf<PS>) void blind_rotate_ps_kernel(
     const LinDesc* __restrict__ descs, int count, const double* __restrict__ bk_ntt,
-    const typename Poly<PS::Nbit>::Tables* __restrict__ gt, int steps, uint32_t* __restrict__ acc_dump)
+    const typename Poly<PS::Nbit>::Tables* __restrict__ gt, int steps, uint32_t* __restrict__ acc_dump, const uint32_t* __restrict__ tvs)
 {
     using D = PsDims<PS>;
     using PO = PsWgPolyOf<PS>;
@@ -331,14 +362,22 @@ __global__ __launch_bounds__(64 * kPsWavesOf<PS>) void blind_rotate_ps_kernel(
     uint32_t* bbar_slot = (uint32_t*)(smem + L::abar + kAbarBytes);
 
     const LinDesc d = descs[g];
+    const int oshift = TV ? desc_shift(d.pad) : 0;        // 0 for every rotation but a multi-output user gate's
     for (int i = tid; i <= PS::n; i += L::threads) {      // pre-add and modulus switch, :316-345
         const uint32_t c = (uint32_t)d.ca * d.in0[i] + (uint32_t)d.cb * d.in1[i];
-        if (i < PS::n) abar_lds[i] = (uint16_t)((c + (1u << (32 - 2 - PS::Nbit))) >> (32 - 1 - PS::Nbit));
-        else *bbar_slot = 2 * N - ((c + d.off) >> (32 - 1 - PS::Nbit));
+        if (i < PS::n) abar_lds[i] = (uint16_t)ps_ms_abar<PS>(c, oshift);
+        else *bbar_slot = ps_ms_bbar<PS>(c + d.off, oshift);
     }
     for (int i = tid; i < D::SUMS * N; i += L::threads) sumL[i] = 0.0;
     __syncthreads();
-    {   // RotatedTestVector, :29-52: mask components zero, body +-mu
+    if (TV && d.pad) {   // a user gate: mask components zero, body X^bbar TV
+        const uint32_t bbar = *bbar_slot;
+        const uint32_t* tv = ps_desc_tv<PS>(tvs, d.pad);
+        for (int e = tid; e < N; e += L::threads) {
+            for (int j = 0; j < PS::k; j++) accL[j * N + e] = 0;
+            accL[PS::k * N + e] = ps_rotated_tv_coef<PS>(tv, bbar, (uint32_t)e);
+        }
+    } else {       // RotatedTestVector, :29-52: mask components zero, body +-mu
         const uint32_t bbar = *bbar_slot;
         for (int e = tid; e < N; e += L::threads) {
             const bool neg = (bbar != 2 * N) && (((uint32_t)e < (bbar & (N - 1))) != ((bbar >> PS::Nbit) != 0));
@@ -462,6 +501,15 @@ __global__ __launch_bounds__(64 * kPsWavesOf<PS>) void blind_rotate_ps_kernel(
             o[e] = m == 0 ? accL[j * N] : 0u - accL[j * N + N - m];
         }
         if (tid == 0) o[PS::k * N] = accL[PS::k * N];
+        // outputs x = 1 .. 2^s - 1 of a multi-output user gate, extracted at index x: a'[m] = a[x - m] (m <= x), -a[N + x - m] (m > x)
+        for (int x = 1; x < (1 << oshift); x++) {
+            o += PS::k * N + 1;
+            for (int e = tid; e < PS::k * N; e += L::threads) {
+                const int j = e / N, m = e % N;
+                o[e] = m <= x ? accL[j * N + x - m] : 0u - accL[j * N + N + x - m];
+            }
+            if (tid == 0) o[PS::k * N] = accL[PS::k * N + x];
+        }
     }
 }
 
@@ -556,10 +604,10 @@ __device__ __forceinline__ void ps_rotate_sub(uint32_t (&temp)[R], const uint32_
     for (int r = 0; r < R; r++) temp[r] = (rot[r] - acc[r] + ps_decomp_offset<PS>()) ^ ps_decomp_signmask<PS>();
 }
 
-template <class PS>
+template <class PS, bool TV>
 __global__ __launch_bounds__(64 * kPsbWavesOf<PS>, kPsbWavesOf<PS> / 4) void blind_rotate_ps_batch_kernel(
     const LinDesc* __restrict__ descs, int count, const double* __restrict__ bk_ntt,
-    const typename Poly<PS::Nbit>::Tables* __restrict__ gt, int steps, uint32_t* __restrict__ acc_dump)
+    const typename Poly<PS::Nbit>::Tables* __restrict__ gt, int steps, uint32_t* __restrict__ acc_dump, const uint32_t* __restrict__ tvs)
 {
     using D = PsDims<PS>;
     using PO = PsbPolyOf<PS>;
@@ -589,14 +637,17 @@ __global__ __launch_bounds__(64 * kPsbWavesOf<PS>, kPsbWavesOf<PS> / 4) void bli
     }
 
     const LinDesc d = descs[g];
+    // one descriptor per wave: the user-gate branches below are wave-uniform.  pad = 0 for every rotation but a user gate's
+    const uint32_t pad = TV ? __builtin_amdgcn_readfirstlane(d.pad) : 0u;
+    const int oshift = desc_shift(pad);
     uint32_t bword = 0;       // pre-add and modulus switch, :316-345
     for (int i = lane; i <= PS::n; i += 64) {
         const uint32_t c = (uint32_t)d.ca * d.in0[i] + (uint32_t)d.cb * d.in1[i];
-        if (i < PS::n) abar_lds[i] = (uint16_t)((c + (1u << (32 - 2 - PS::Nbit))) >> (32 - 1 - PS::Nbit));
+        if (i < PS::n) abar_lds[i] = (uint16_t)ps_ms_abar<PS>(c, oshift);
         else bword = c;
     }
     bword = __builtin_amdgcn_readlane(bword, PS::n % 64) + d.off;
-    const uint32_t bbar = 2 * N - (bword >> (32 - 1 - PS::Nbit));
+    const uint32_t bbar = ps_ms_bbar<PS>(bword, oshift);
     uint32_t acc[K1][R];      // RotatedTestVector, :29-52: mask components zero, body +-mu
 #pragma unroll
     for (int r = 0; r < R; r++) {
@@ -605,6 +656,11 @@ __global__ __launch_bounds__(64 * kPsbWavesOf<PS>, kPsbWavesOf<PS> / 4) void bli
 #pragma unroll
         for (int j = 0; j < PS::k; j++) acc[j][r] = 0;
         acc[PS::k][r] = neg ? 0u - kMu : kMu;
+    }
+    if (pad) {                // a user gate: body X^bbar TV instead, R coefficients per lane gathered once, before any key row is used
+        const uint32_t* tv = ps_desc_tv<PS>(tvs, pad);
+#pragma unroll
+        for (int r = 0; r < R; r++) acc[PS::k][r] = ps_rotated_tv_coef<PS>(tv, bbar, lane + 64 * r);
     }
     __syncthreads();          // tables staged; abar list visible
     typename PO::State po_state;
@@ -729,6 +785,21 @@ __global__ __launch_bounds__(64 * kPsbWavesOf<PS>, kPsbWavesOf<PS> / 4) void bli
                 else o[j * N + N - e] = 0u - acc[j][r];
             }
         if (lane == 0) o[PS::k * N] = acc[PS::k][0];
+        // outputs x = 1 .. 2^s - 1 of a multi-output user gate: coefficient e of a_j goes to a'[x - e] (e <= x) or, negated, to
+        // a'[N + x - e]; b' = b[x], which lane x holds in register 0 (x < 8)
+#pragma unroll 1
+        for (int x = 1; x < (1 << oshift); x++) {
+            o += PS::k * N + 1;
+#pragma unroll
+            for (int j = 0; j < PS::k; j++)
+#pragma unroll
+                for (int r = 0; r < R; r++) {
+                    const int e = lane + 64 * r;
+                    if (e <= x) o[j * N + x - e] = acc[j][r];
+                    else o[j * N + N + x - e] = 0u - acc[j][r];
+                }
+            if (lane == x) o[PS::k * N] = acc[PS::k][0];
+        }
     }
 }
 

@@ -133,6 +133,7 @@ struct Lvl2Path {
     static constexpr int lvl0_words = kLvl0Words, mid_words = k2Words, n = kLvl0N;
     static constexpr uint64_t ks_mu = k2Mu;
     static constexpr bool lvl1_gates = false, user_gates = false, lvl2_user_gates = true;
+    static constexpr int set_index = -1;
     // the ring's own definitions (cufhe_amd_lvl2_define_gate): an op of cufhe_amd_define_gate stays refused here
     static const UserGate* user_op(int op) { return lvl2_user_gate(op); }
     static uint32_t tv_pad(int op, const UserGate& u) { return u.tv ? make_pad2(lvl2_user_def(op), 0) : 0u; }

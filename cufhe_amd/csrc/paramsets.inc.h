@@ -9,10 +9,12 @@
 namespace {
 
 struct PsState {
-    bool ready = false, lds_opt_in = false, ks_lds_opt_in = false;
+    bool ready = false, lds_opt_in = false, lds_opt_in_tv = false, ks_lds_opt_in = false;
     double* bk_ntt = nullptr;
     uint32_t* ksk = nullptr;
     uint32_t* ksk_padded = nullptr;   // sets whose key switch has the default shape: rows padded for keyswitch_kernel
+    uint32_t* tvs = nullptr;          // [kMaxUserGates][N]: the test vectors of the set's user gates (cufhe_amd_ps_define_gate), allocated
+                                      // by the first definition that has one; kept when the set's keys are replaced, freed by CleanUp
 };
 
 // kN = 1024, n = 630, t = 8, basebit = 2: the hand-scheduled shared-table key switch of kernels.hip.h applies as it is
@@ -67,27 +69,37 @@ const typename Poly<PS::Nbit>::Tables* ps_tables_batch(DeviceState& s)
     else return s.tables512 + 2;
 }
 
-template <class PS>
-int ps_launch_blind_rotate(DeviceState& s, PsState& ps, hipStream_t st, const LinDesc* d, size_t count, int steps, uint32_t* dump)
+// user: some descriptor of the launch is a user gate's (LinDesc::pad != 0): the <true> instantiations, which read pad and the set's
+// table; every other launch runs the <false> ones
+template <class PS, bool TV>
+int ps_launch_blind_rotate_tv(DeviceState& s, PsState& ps, hipStream_t st, const LinDesc* d, size_t count, int steps, uint32_t* dump)
 {
-    if (count == 0) return 0;
-    ProfScope prof{s, st, count, false};
-    if (int rc = prof.begin()) return rc;
-    if (!ps.lds_opt_in) {
-        HIP_TRY(hipFuncSetAttribute((const void*)blind_rotate_ps_kernel<PS>, hipFuncAttributeMaxDynamicSharedMemorySize, PsLds<PS>::bytes));
-        HIP_TRY(hipFuncSetAttribute((const void*)blind_rotate_ps_batch_kernel<PS>, hipFuncAttributeMaxDynamicSharedMemorySize, PsbLds<PS>::bytes));
-        ps.lds_opt_in = true;
+    bool& opt_in = TV ? ps.lds_opt_in_tv : ps.lds_opt_in;
+    if (!opt_in) {
+        HIP_TRY(hipFuncSetAttribute((const void*)blind_rotate_ps_kernel<PS, TV>, hipFuncAttributeMaxDynamicSharedMemorySize, PsLds<PS>::bytes));
+        HIP_TRY(hipFuncSetAttribute((const void*)blind_rotate_ps_batch_kernel<PS, TV>, hipFuncAttributeMaxDynamicSharedMemorySize, PsbLds<PS>::bytes));
+        opt_in = true;
     }
     if (plan::ps_use_batch(count, PS::limbs, PS::Nbit, cus_of(s), g_tuning)) {
         // one wave per rotation, 8 rotations per workgroup share the key rows (throughput shape)
         const unsigned blocks = (unsigned)((count + PsbLds<PS>::waves - 1) / PsbLds<PS>::waves);
-        hipLaunchKernelGGL(blind_rotate_ps_batch_kernel<PS>, dim3(blocks), dim3(PsbLds<PS>::threads), PsbLds<PS>::bytes, st, d, (int)count,
-                           ps.bk_ntt, ps_tables_batch<PS>(s), steps, dump);
+        hipLaunchKernelGGL((blind_rotate_ps_batch_kernel<PS, TV>), dim3(blocks), dim3(PsbLds<PS>::threads), PsbLds<PS>::bytes, st, d, (int)count,
+                           ps.bk_ntt, ps_tables_batch<PS>(s), steps, dump, ps.tvs);
     } else {
         // one workgroup per rotation (latency shape)
-        hipLaunchKernelGGL(blind_rotate_ps_kernel<PS>, dim3((unsigned)count), dim3(PsLds<PS>::threads), PsLds<PS>::bytes, st, d, (int)count,
-                           ps.bk_ntt, kPsWgR4 ? ps_tables_batch<PS>(s) : ps_tables<PS>(s), steps, dump);
+        hipLaunchKernelGGL((blind_rotate_ps_kernel<PS, TV>), dim3((unsigned)count), dim3(PsLds<PS>::threads), PsLds<PS>::bytes, st, d, (int)count,
+                           ps.bk_ntt, kPsWgR4 ? ps_tables_batch<PS>(s) : ps_tables<PS>(s), steps, dump, ps.tvs);
     }
+    return 0;
+}
+template <class PS>
+int ps_launch_blind_rotate(DeviceState& s, PsState& ps, hipStream_t st, const LinDesc* d, size_t count, int steps, uint32_t* dump, bool user)
+{
+    if (count == 0) return 0;
+    ProfScope prof{s, st, count, false};
+    if (int rc = prof.begin()) return rc;
+    if (int rc = user ? ps_launch_blind_rotate_tv<PS, true>(s, ps, st, d, count, steps, dump) : ps_launch_blind_rotate_tv<PS, false>(s, ps, st, d, count, steps, dump))
+        return rc;
     HIP_TRY(hipGetLastError());
     return prof.commit();
 }
@@ -106,6 +118,15 @@ int ps_launch_cmux(DeviceState& s, hipStream_t st, const CmuxDesc* d, size_t cou
     return 0;
 }
 
+// index of PS in CompiledSets: the `set` of the C ABI
+template <class PS, size_t I = 0>
+constexpr int ps_index_of()
+{
+    static_assert(I < std::tuple_size_v<CompiledSets>, "not a compiled parameter set");
+    if constexpr (std::is_same_v<PS, std::tuple_element_t<I, CompiledSets>>) return (int)I;
+    else return ps_index_of<PS, I + 1>();
+}
+
 // A parameter set for lower_gates / lower_trlwe_ops (capi.hip)
 template <class PS>
 struct PsPath {
@@ -115,13 +136,25 @@ struct PsPath {
     using Mid = uint32_t;
     static constexpr int lvl0_words = D::lvl0_words, mid_words = D::lvl1_words, n = PS::n;
     static constexpr uint32_t ks_mu = kMu;
-    static constexpr bool lvl1_gates = true, has_cmux = !PS::small_modulus, user_gates = false, packed_rom = false, lvl2_user_gates = false;
+    static constexpr bool lvl1_gates = true, has_cmux = !PS::small_modulus, user_gates = true, packed_rom = false, lvl2_user_gates = false;
+    // the set's own definitions (cufhe_amd_ps_define_gate made for this set): ids of cufhe_amd_define_gate, of cufhe_amd_lvl2_define_gate
+    // and of another set's definitions stay refused here (lower_gates)
+    static constexpr int set_index = ps_index_of<PS>();
+    static const UserGate* user_op(int op) { return ps_user_gate(op, set_index); }
+    static int user_def(int op) { return ps_user_def(op); }
+    static int user_output(int op) { return ps_user_output(op); }
+    static uint32_t multi_pad(int op, const UserGate& u) { return make_pad(ps_user_def(op), u.s); }
+    static uint32_t tv_pad(int op, const UserGate& u) { return u.tv ? make_pad(ps_user_def(op), 0) : 0u; }
     static constexpr size_t trlwe_words = (size_t)D::K1 * D::N;
     static constexpr auto se_kernel = sample_extract_ps_kernel<PS>;
     DeviceState& s;
     PsState& ps;
     int ready() const { return ps.ready ? 0 : fail(-3, "cufhe_amd_ps_initialize has not been called for this parameter set and device"); }
-    int rotate(hipStream_t st, const LinDesc* d, size_t count, int steps, uint32_t* dump) const { return ps_launch_blind_rotate<PS>(s, ps, st, d, count, steps, dump); }
+    // tv_rows: some descriptor names a test-vector row (lower_gates; false for every launch without user gates)
+    int rotate(hipStream_t st, const LinDesc* d, size_t count, int steps, uint32_t* dump, bool tv_rows = false) const
+    {
+        return ps_launch_blind_rotate<PS>(s, ps, st, d, count, steps, dump, tv_rows);
+    }
     int keyswitch(hipStream_t st, const LinDesc* d, size_t count) const { return ps_launch_keyswitch<PS>(s, ps, st, d, count); }
     int cmux(hipStream_t st, const CmuxDesc* d, size_t count) const { return ps_launch_cmux<PS>(s, st, d, count); }
 };
@@ -202,8 +235,42 @@ void ps_release(int device)
         (void)hipFree(ps.bk_ntt);
         (void)hipFree(ps.ksk);
         if (ps.ksk_padded) (void)hipFree(ps.ksk_padded);
+        if (ps.tvs) (void)hipFree(ps.tvs);
         ps = PsState{};
     }
+}
+
+// definition k = g_ps_user_count of a user gate of parameter set `set` with nout = 2^sh outputs (1: cufhe_amd_ps_define_gate); the
+// caller holds g_mu
+int define_ps_user_gate(int set, const int32_t coeffs[3], uint32_t offset, const uint32_t* test_vector, int sh, int* op)
+{
+    if (!coeffs || !op) return fail(-1, "null pointer");
+    if (coeffs[0] == 0) return fail(-1, "parameter set user gate: c0 must not be 0");
+    return ps_dispatch(set, [&](auto psx) -> int {
+        constexpr size_t N = PsDims<decltype(psx)>::N;
+        for (int i = 0; i < g_gpu_num; i++)
+            if (!ps_state(set, i).ready) return fail(-3, "cufhe_amd_ps_initialize has not been called for this parameter set on every device");
+        const int k = g_ps_user_count.load(std::memory_order_relaxed);
+        if (k >= kMaxUserGates) return fail(-1, "parameter set user gate table full (CUFHE_AMD_PS_MAX_USER_GATES definitions until CleanUp)");
+        if (test_vector) {
+            // row k of the set's table on every device, synchronously (like the key replicas); no launch reads the row before its id exists
+            for (int i = 0; i < g_gpu_num; i++) {
+                PsState& ps = ps_state(set, i);
+                HIP_TRY(hipSetDevice(phys_device(i)));
+                if (!ps.tvs) {
+                    DevPtr<uint32_t> t;
+                    HIP_TRY(t.alloc((size_t)kMaxUserGates * N));
+                    ps.tvs = t.release();
+                }
+                HIP_TRY(hipMemcpy(ps.tvs + (size_t)k * N, test_vector, N * sizeof(uint32_t), hipMemcpyHostToDevice));
+            }
+        }
+        g_ps_user[k] = UserGate{{coeffs[0], coeffs[1], coeffs[2]}, offset, test_vector != nullptr, 1 << sh, sh};
+        g_ps_user_set[k] = set;
+        g_ps_user_count.store(k + 1, std::memory_order_release);
+        *op = CUFHE_AMD_PS_USER_OP_BASE + k;
+        return 0;
+    });
 }
 
 }  // namespace
@@ -271,7 +338,9 @@ int cufhe_amd_ps_initialize(int set, const uint32_t* bk, size_t bk_words, const 
                 if (ps.ksk_padded) (void)hipFree(ps.ksk_padded);
             }
             Built& b = built[(size_t)i];
+            uint32_t* tvs = ps.tvs;              // the set's user gates outlive a change of its keys
             ps = PsState{};
+            ps.tvs = tvs;
             ps.bk_ntt = b.bk_ntt.release();
             ps.ksk = b.ksk.release();
             ps.ksk_padded = b.ksk_padded.release();
@@ -343,6 +412,92 @@ int cufhe_amd_ps_blind_rotate_batch(int set, int device, void* stream, size_t co
         hipStream_t st = (hipStream_t)stream;
         return direct_batch(p.s, st, count, [&](size_t g) { return LinDesc{tlwe0 + g * D::lvl0_words, tlwe0 + g * D::lvl0_words, nullptr, 1, 0, 0u, 0u}; },
                             [&](const LinDesc* d) { return p.rotate(st, d, count, st_steps, acc); });
+    });
+}
+
+int cufhe_amd_ps_define_gate(int set, const int32_t coeffs[3], uint32_t offset, const uint32_t* test_vector, int* op)
+{
+    std::lock_guard<std::mutex> lk(g_mu);
+    return define_ps_user_gate(set, coeffs, offset, test_vector, 0, op);
+}
+
+int cufhe_amd_ps_define_gate_multi(int set, const int32_t coeffs[3], uint32_t offset, int nout, const uint32_t* test_vector, int* op)
+{
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (nout != 2 && nout != 4 && nout != 8) return fail(-1, "multi-output user gate of a parameter set: nout must be 2, 4 or 8");
+    if (!test_vector) return fail(-1, "multi-output user gate of a parameter set: the test vector is required (cufhe_amd_ps_test_vector_multi)");
+    return define_ps_user_gate(set, coeffs, offset, test_vector, nout == 2 ? 1 : nout == 4 ? 2 : 3, op);
+}
+
+int cufhe_amd_ps_test_vector_multi(int set, const uint32_t* values, int p, int nout, uint32_t* tv)
+{
+    if (!values || !tv) return fail(-1, "null pointer");
+    if (nout != 1 && nout != 2 && nout != 4 && nout != 8) return fail(-1, "nout must be 1, 2, 4 or 8");
+    return ps_dispatch(set, [&](auto psx) -> int {
+        constexpr int N = PsDims<decltype(psx)>::N;
+        if (p < 2 || (p & (p - 1)) || p > N / 2 || p * nout > N / 2) return fail(-1, "p must be a power of two >= 2 with p nout <= N/2 of the parameter set");
+        // the boxes of cufhe_amd_test_vector_multi on the set's N: TV[nout q + j] = values[j][m], m the box of position nout q (the top
+        // half-box, m = p, is the wrap of m = 0's lower half: -values[j][0])
+        const int box = N / p;
+        for (int q = 0; q < N / nout; q++) {
+            const int m = (nout * q + box / 2) / box;
+            for (int j = 0; j < nout; j++) {
+                const uint32_t* v = values + (size_t)j * p;
+                tv[nout * q + j] = m == p ? 0u - v[0] : v[m];
+            }
+        }
+        return 0;
+    });
+}
+
+int cufhe_amd_ps_test_vector(int set, const uint32_t* values, int p, uint32_t* tv) { return cufhe_amd_ps_test_vector_multi(set, values, p, 1, tv); }
+
+/* The parity hook of a set's user gates: `count` evaluations of definition `op` on [count][n + 1] lvl0 arrays with the rotation
+ * descriptors of the gate path (lower_gates: arity, the pre-added c0 in0 + c1 in1 of three operands, the pad); acc[count][(k+1) N]
+ * receives the accumulators after `steps` CMux steps (negative: all).  A multi-output definition is named by output 0's id. */
+int cufhe_amd_ps_user_rotate(int set, int device, void* stream, size_t count, int op, const uint32_t* in0, const uint32_t* in1,
+                             const uint32_t* in2, uint32_t* acc, int steps)
+{
+    if (int rc = use_device(device)) return rc;
+    return ps_dispatch(set, [&](auto psx) -> int {
+        using PS = decltype(psx);
+        using P = PsPath<PS>;
+        constexpr size_t w0 = P::lvl0_words;
+        if (!is_ps_user_op(op)) return fail(-1, "op is not in the parameter sets' user gate id range (CUFHE_AMD_PS_USER_OP_BASE + k)");
+        const UserGate* u = ps_user_gate(op, set);
+        if (!u) return fail_ps_user_op(op, set);
+        if (ps_user_output(op) != 0) return fail(-1, "the accumulator of a multi-output definition is dumped under output 0's id");
+        const P p{g_dev[device], ps_state(set, device)};
+        if (int rc = p.ready()) return rc;
+        if (!in0 || !acc) return fail(-1, "null pointer");
+        const int arity = user_gate_arity(*u);
+        if (arity >= 2 && !in1) return fail(-1, "user gate needs a second operand");
+        if (arity == 3 && !in2) return fail(-1, "user gate needs a third operand");
+        if (count == 0) return 0;
+        hipStream_t st = (hipStream_t)stream;
+        Scratch sc;
+        if (int rc = open_scratch(p.s, st, count * (2 * sizeof(LinDesc) + (arity == 3 ? w0 * sizeof(uint32_t) : 0)) + 8192, &sc)) return rc;
+        uint32_t* tmpp = nullptr;
+        if (arity == 3)
+            if (int rc = sc.alloc((void**)&tmpp, count * w0 * sizeof(uint32_t))) return rc;
+        const uint32_t pad = u->nout > 1 ? P::multi_pad(op, *u) : P::tv_pad(op, *u);
+        std::vector<LinDesc> rot(count), pre;
+        for (size_t g = 0; g < count; g++) {
+            const uint32_t* a = in0 + g * w0;
+            const uint32_t* b = arity >= 2 ? in1 + g * w0 : a;
+            int32_t ca = u->c[0], cb = u->c[1];
+            if (arity == 3) {
+                uint32_t* t = tmpp + g * w0;
+                pre.push_back({a, b, t, u->c[0], u->c[1], 0u, 0u});
+                a = t; b = in2 + g * w0; ca = 1; cb = u->c[2];
+            }
+            rot[g] = LinDesc{a, b, nullptr, ca, cb, u->off, pad};
+        }
+        LinDesc *drot, *dpre;
+        if (int rc = upload_descs(p.s, sc, rot, &drot)) return rc;
+        if (int rc = upload_descs(p.s, sc, pre, &dpre)) return rc;
+        if (int rc = launch_lincomb(st, dpre, pre.size(), (int)w0)) return rc;
+        return p.rotate(st, drot, count, (steps < 0 || steps > PS::n) ? PS::n : steps, acc, pad != 0);
     });
 }
 

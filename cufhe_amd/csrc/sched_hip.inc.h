@@ -453,9 +453,16 @@ int cufhe_amd_enqueue_gate(int device, void* stream, int op, int copying, cufhe_
         if (g_param_set >= 0 || g_lvl0_ring != 2048 || out->level != 0) return fail_lvl2_user_path();
         if (!(u = lvl2_user_gate(op))) return fail_lvl2_user_op(op);
     }
+    // a user gate of a parameter set (cufhe_amd_ps_define_gate): the same, at either level, while "param_set" is the set it was made for
+    const bool ups = is_ps_user_op(op);
+    if (ups) {
+        if (!out || !in0) return fail(-1, "null ciphertext");
+        if (g_param_set < 0 || (g_lvl0_ring == 2048 && out->level == 0)) return fail_ps_user_path();
+        if (!(u = ps_user_gate(op, (int)g_param_set))) return fail_ps_user_op(op, (int)g_param_set);
+    }
     if (!u && (op < 0 || op >= CUFHE_AMD_NUM_OPS)) return fail(-1, "unknown gate op");
     if (!out || !in0) return fail(-1, "null ciphertext");
-    if (u && !u2 && (g_param_set >= 0 || (g_lvl0_ring == 2048 && out->level == 0)))
+    if (u && !u2 && !ups && (g_param_set >= 0 || (g_lvl0_ring == 2048 && out->level == 0)))
         return fail(-1, "user gates run on the default path only: not with \"param_set\" active or on the N = 2048 ring (\"lvl0_ring\")");
     const bool three = op == CUFHE_AMD_MUX || op == CUFHE_AMD_NMUX || (u && user_gate_arity(*u) == 3);
     const bool one = op == CUFHE_AMD_NOT || op == CUFHE_AMD_COPY || (u && user_gate_arity(*u) == 1);
@@ -482,6 +489,9 @@ int cufhe_amd_enqueue_gate_multi(int device, void* stream, int op, int copying, 
     std::lock_guard<std::mutex> lk(g_sched_mu);
     if (int rc = check_device(device)) return rc;
     if (is_lvl2_user_op(op)) return fail(-1, "enqueue_gate_multi: lvl2 user gates have one output (cufhe_amd_enqueue_gate)");
+    if (is_ps_user_op(op))
+        return fail(-1, "enqueue_gate_multi: the outputs of a parameter set's user gate are recorded one by one (cufhe_amd_enqueue_gate with "
+                        "CUFHE_AMD_PS_USER_OP_OUTPUT(op, j)); siblings on the same operands in one flush share the rotation");
     const UserGate* u = user_gate(op);
     if (is_user_op(op) && !u) return fail_user_op(op);
     if (!u || user_output(op) != 0 || u->nout < 2) return fail(-1, "enqueue_gate_multi: op must be a multi-output user gate (cufhe_amd_define_gate_multi)");

@@ -672,6 +672,43 @@ int cufhe_amd_ps_cmux_batch(int set, int device, void* stream, size_t count, con
  * CUFHE_AMD_TL_SEIKS (trlwe -> tlwe0; SEIandKS, src/keyswitch_gpu.cu:26-40) */
 int cufhe_amd_ps_trlwe_op_batch(int set, int device, void* stream, int op, size_t count, uint32_t* out, const uint32_t* in);
 
+/* ---- user gates on a parameter set: programmable bootstrapping with the set's n, N, k ----
+ * cufhe_amd_define_gate word for word, over compiled set `set`: a definition is the linear part x = c0 in0 + c1 in1 + c2 in2 +
+ * (0, .., 0, offset) on ciphertexts of the set (c0 != 0; c2 != 0: three operands, else c1 != 0: two, else one) and a test vector of
+ * N torus words of THAT set (NULL: the constant mu = 2^29, the built-in gates' rotation).  Level 0 is blind rotate from
+ * (0, .., 0, X^bbar TV) -> SampleExtract -> key switch on n + 1 words, level 1 key switch -> blind rotate -> SampleExtract on k N + 1
+ * words, both with the roundings of the set's built-in gates.  The op id returned is CUFHE_AMD_PS_USER_OP_BASE + k for the k-th
+ * definition since the last cufhe_amd_cleanup, over ALL sets together (k < CUFHE_AMD_PS_MAX_USER_GATES): an op of
+ * cufhe_amd_ps_gate_batch[_level] on that set, mixed freely with the built-in ops (still one rotation launch per level), and of
+ * cufhe_amd_gate / _gate_batch / _gate_list / _enqueue_gate while "param_set" is that set.  Definitions are immutable; cufhe_amd_cleanup
+ * drops them.  A definition's test vector is copied to every logical device before the id is returned.
+ * Refused with -1: c0 = 0, a null pointer, the 65th definition, an unknown set; with -3: a set that cufhe_amd_ps_initialize has not
+ * loaded on every logical device.  An op of this range is refused (-1, a message naming parameter sets, before any device work) on the
+ * default path, on the N = 2048 ring, on a set other than its own, and when it names no definition.  The ids of cufhe_amd_define_gate
+ * and cufhe_amd_lvl2_define_gate keep their meaning and stay refused on a set.
+ * On `smallmod` the accumulator holds torus words between CMux steps, so the same initial accumulator serves; the results are the
+ * small-modulus path's (approximate by design, deterministic), as for its built-in gates. */
+#define CUFHE_AMD_PS_USER_OP_BASE 12288      /* 12288 .. 12799: above CUFHE_AMD_TL_CMUX_ROTATE(2N - 1) = 6143 and the lvl2 range 8192 .. 8703 */
+#define CUFHE_AMD_PS_MAX_USER_GATES 64
+int cufhe_amd_ps_define_gate(int set, const int32_t coeffs[3], uint32_t offset, const uint32_t* test_vector /* N of the set, or NULL */, int* op);
+/* Multi-output (cufhe_amd_define_gate_multi on the set): nout = 2, 4 or 8 functions from one rotation.  The modulus switch is rounded
+ * to multiples of nout, the test vector is the interleaved one of cufhe_amd_ps_test_vector_multi and is required; output j is
+ * SampleExtract at index j of the one accumulator and has the op id CUFHE_AMD_PS_USER_OP_OUTPUT(op, j) = op + 64 j.  Outputs of one
+ * definition on the same operands in one list (or one flush of the scheduler) share the rotation, whatever their order; requesting
+ * only some of them is allowed.  cufhe_amd_enqueue_gate_multi refuses these ids: record each output with cufhe_amd_enqueue_gate. */
+#define CUFHE_AMD_PS_USER_OP_OUTPUT(op, j) ((op) + (j) * CUFHE_AMD_PS_MAX_USER_GATES)
+int cufhe_amd_ps_define_gate_multi(int set, const int32_t coeffs[3], uint32_t offset, int nout /* 2, 4, 8 */, const uint32_t* test_vector, int* op);
+/* Host only (no device, no keys): the boxes of cufhe_amd_test_vector[_multi] with the set's N.  values[p] (multi: values[nout][p]) are
+ * the output torus words of messages m = 0 .. p - 1 encoded as m 2^32 / (2p) with a padding bit; coefficient j lies in the box of
+ * m = round(j p / N), the top half-box is -values[0].  p a power of two, 2 <= p <= N/2; multi: nout in {1, 2, 4, 8}, p nout <= N/2. */
+int cufhe_amd_ps_test_vector(int set, const uint32_t* values, int p, uint32_t* tv);
+int cufhe_amd_ps_test_vector_multi(int set, const uint32_t* values, int p, int nout, uint32_t* tv);
+/* Parity hook (the counterpart of cufhe_amd_lvl2_user_rotate_batch): in0/in1/in2[count][n + 1] lvl0 operands (as many as the
+ * definition's arity; the others may be NULL) -> acc[count][(k+1) N], the accumulators of definition `op` (a multi-output definition:
+ * output 0's id) after `steps` CMux steps (negative: all n), so that the first steps can be checked word for word. */
+int cufhe_amd_ps_user_rotate(int set, int device, void* stream, size_t count, int op,
+                             const uint32_t* in0, const uint32_t* in1, const uint32_t* in2, uint32_t* acc, int steps);
+
 /* ---- measurement ----
  * When enabled, every blind-rotate / key-switch launch is bracketed by HIP events on the
  * stream it runs on; get_profile synchronises and returns accumulated kernel time.

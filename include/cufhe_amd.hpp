@@ -355,13 +355,21 @@ struct UserGate {
     /// the op id of output j (a single-output op wherever a built-in op is accepted)
     int output(int j) const { return CUFHE_AMD_USER_OP_OUTPUT(op, j); }
 };
-/// Define after Initialize; tv: N = 1024 lvl1 torus words (nullptr: the constant mu).  Valid until CleanUp.  nout = 2, 4 or 8: a
-/// multi-output gate whose interleaved tv (TestVectorMulti) is required.
+/// Define after Initialize; tv: N lvl1 torus words of this build's set (nullptr: the constant mu).  Valid until CleanUp.  nout = 2, 4
+/// or 8: a multi-output gate whose interleaved tv (TestVectorMulti) is required.  On the BASELINE numbers the gate is one of
+/// cufhe_amd_define_gate; when Initialize has put the per-gate API on another compiled set (kParamSetIndex > 0) it is one of
+/// cufhe_amd_ps_define_gate for that set, with that set's N -- the same handle for Apply / gApply / ApplyMulti / Output either way.
+static_assert(CUFHE_AMD_PS_MAX_USER_GATES == CUFHE_AMD_MAX_USER_GATES, "UserGate::output serves the parameter sets' id rule too");
 inline UserGate DefineGate(const std::array<int32_t, 3>& coeffs, uint32_t offset, const uint32_t* tv = nullptr, int nout = 1)
 {
     UserGate g;
-    if (nout == 1) CUFHE_AMD_CHECK(cufhe_amd_define_gate(coeffs.data(), offset, tv, &g.op));
-    else CUFHE_AMD_CHECK(cufhe_amd_define_gate_multi(coeffs.data(), offset, nout, tv, &g.op));
+    if (kParamSetIndex != 0) {
+        if (nout == 1) CUFHE_AMD_CHECK(cufhe_amd_ps_define_gate(kParamSetIndex, coeffs.data(), offset, tv, &g.op));
+        else CUFHE_AMD_CHECK(cufhe_amd_ps_define_gate_multi(kParamSetIndex, coeffs.data(), offset, nout, tv, &g.op));
+    } else {
+        if (nout == 1) CUFHE_AMD_CHECK(cufhe_amd_define_gate(coeffs.data(), offset, tv, &g.op));
+        else CUFHE_AMD_CHECK(cufhe_amd_define_gate_multi(coeffs.data(), offset, nout, tv, &g.op));
+    }
     g.nout = nout;
     return g;
 }
@@ -371,15 +379,17 @@ inline std::vector<uint32_t> TestVectorMulti(const std::vector<std::vector<uint3
     std::vector<uint32_t> flat;
     for (const auto& v : values) flat.insert(flat.end(), v.begin(), v.begin() + std::min<size_t>(v.size(), (size_t)p));
     if (flat.size() != values.size() * (size_t)p) CUFHE_AMD_CHECK(-1);
-    std::vector<uint32_t> tv(1024);
-    CUFHE_AMD_CHECK(cufhe_amd_test_vector_multi(flat.data(), p, (int)values.size(), tv.data()));
+    std::vector<uint32_t> tv(kParamSetIndex != 0 ? (size_t)TFHEpp::lvl1param::n : (size_t)1024);
+    if (kParamSetIndex != 0) CUFHE_AMD_CHECK(cufhe_amd_ps_test_vector_multi(kParamSetIndex, flat.data(), p, (int)values.size(), tv.data()));
+    else CUFHE_AMD_CHECK(cufhe_amd_test_vector_multi(flat.data(), p, (int)values.size(), tv.data()));
     return tv;
 }
 /// the test vector of a function on values.size() messages (a power of two, 2 .. N/2) with a padding bit, m -> m 2^32 / (2p)
 inline std::vector<uint32_t> TestVector(const std::vector<uint32_t>& values)
 {
-    std::vector<uint32_t> tv(1024);             // user gates run on the default set only: N = 1024 whatever the build selects
-    CUFHE_AMD_CHECK(cufhe_amd_test_vector(values.data(), (int)values.size(), tv.data()));
+    std::vector<uint32_t> tv(kParamSetIndex != 0 ? (size_t)TFHEpp::lvl1param::n : (size_t)1024);      // N of the set the gates run on
+    if (kParamSetIndex != 0) CUFHE_AMD_CHECK(cufhe_amd_ps_test_vector(kParamSetIndex, values.data(), (int)values.size(), tv.data()));
+    else CUFHE_AMD_CHECK(cufhe_amd_test_vector(values.data(), (int)values.size(), tv.data()));
     return tv;
 }
 /// A user gate of the N = 2048 ring (cufhe_amd_lvl2_define_gate): define after lvl2::Initialize; tv: N2 = 2048 uint64 torus words
@@ -428,10 +438,19 @@ template <class P> inline void Apply(UserGate g, Ctxt<P>& out, Ctxt<P>& in0, Ctx
 template <class P> inline void gApply(UserGate g, Ctxt<P>& out, Ctxt<P>& in0, Ctxt<P>& in1, Ctxt<P>& in2, Stream st)
 { CUFHE_AMD_CHECK(cufhe_amd_enqueue_gate(st.device_id(), st.raw(), g.op, 0, out.handle, in0.handle, in1.handle, in2.handle)); }
 /// ApplyMulti: all g.nout outputs of one evaluation of a multi-output gate (one rotation), outs[j] <- output j; gApplyMulti: device
-/// buffers only.  No output may be an input, no two outputs the same ciphertext.
+/// buffers only.  No output may be an input, no two outputs the same ciphertext.  On a compiled set other than the BASELINE one the
+/// outputs are recorded one by one (cufhe_amd_enqueue_gate): recorded together on the same operands, they still share the rotation.
 template <class P>
 inline void apply_multi(UserGate g, int copying, std::initializer_list<Ctxt<P>*> outs, Ctxt<P>* in0, Ctxt<P>* in1, Ctxt<P>* in2, Stream st)
 {
+    if (kParamSetIndex != 0) {
+        if ((int)outs.size() != g.nout) CUFHE_AMD_CHECK(-1);
+        int j = 0;
+        for (Ctxt<P>* o : outs)
+            CUFHE_AMD_CHECK(cufhe_amd_enqueue_gate(st.device_id(), st.raw(), g.output(j++), copying, o->handle, in0->handle,
+                                                   in1 ? in1->handle : nullptr, in2 ? in2->handle : nullptr));
+        return;
+    }
     std::vector<cufhe_amd_ctxt*> h;
     for (Ctxt<P>* o : outs) h.push_back(o->handle);
     CUFHE_AMD_CHECK(cufhe_amd_enqueue_gate_multi(st.device_id(), st.raw(), g.op, copying, (int)h.size(), h.data(), in0->handle,
