@@ -275,6 +275,13 @@ def CircuitBootstrapping(out, inp, st):
     _trlwe_op(TL_CIRCUIT_BOOTSTRAP, True, out, inp, st)
 
 
+def TRGSW2NTT(out, trgsw, st):                             # src/bootstrap_gpu.cu:75-94
+    """out (TrgswNtt) <- the NTT-domain words of the torus-domain TRGSW `trgsw` ((k+1) l (k+1) N uint32): written to out.trgswhost
+    before the call returns, their upload to the stream's device recorded like a CtxtCopyH2D (cufhe_amd_trgsw_to_ntt)"""
+    t = np.ascontiguousarray(trgsw, dtype=np.uint32)
+    check(lib.cufhe_amd_trgsw_to_ntt(st.device_id(), st.st(), t.ctypes.data, out._h))
+
+
 def CtxtCopyH2D(c, st):
     check(lib.cufhe_amd_enqueue_copy(st.device_id(), st.st(), c._h, 1))
 

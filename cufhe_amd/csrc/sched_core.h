@@ -752,6 +752,7 @@ class DeviceSched {
     std::vector<Plan*> plan_pool_;              // retired levels, vectors keep their capacity
     uint32_t group_floor_ = 0;                  // record_gate_group: the level all outputs of the evaluation take
     bool hold_flush_ = false;                   // record_gate_group: no flush between the outputs of one evaluation
+    bool group_inputs_fresh_ = false;           // record_gate_group: an earlier output of this evaluation has refreshed the operands from tlwehost
     uint64_t next_group_ = 1;
     std::deque<Group*> live_;                   // launched or queued groups, oldest first
     int sticky_error_ = 0;
@@ -1059,9 +1060,11 @@ inline int DeviceSched::record_gate_group(void* stream, const int* ops, bool cop
         uint32_t D = std::max(Din, po.ready);
         if (has_readers(po)) D = std::max(D, max_reader(po) + 1);
         if (!(rename_outputs && outs[j]->level <= 1)) floor = std::max(floor, D);
+        if (copying && po.last_upload >= base_depth_) floor = std::max(floor, po.last_upload);      // (record_gate: a delivery never ahead of a recorded upload)
     }
     group_floor_ = floor;
     hold_flush_ = true;
+    group_inputs_fresh_ = false;
     int rc = 0;
     for (size_t j = 0; j < n && !rc; j++) rc = record_gate(stream, ops[j], copying, outs[j], ins);
     group_floor_ = 0;
@@ -1076,8 +1079,13 @@ inline int DeviceSched::record_gate(void* stream, int op, bool copying, cufhe_am
     if (kind < 0) kind = out->level;
     ScopedNs timer(&stats_.record_ns);
     // inputs that must be refreshed from the host (may wait for another device: do it first)
+    // (the outputs of one evaluation read ONE upload of its operands: the first output's.  A second upload -- which a raw stream handle
+    // that is out would force, see resolve_host -- would follow the first output's read and push its siblings a level back each)
+    // Skipping resolve_host for the later outputs is right ONLY under record_gate_group's precondition, which its callers check
+    // (cufhe_amd_enqueue_gate_multi): no output of the evaluation is one of its operands, so the first output's write cannot have changed
+    // what the operands' buffers hold; same operands, same stream, same call, so its destroyed-operand check and note_upload_stream stand.
     bool need_up[3] = {false, false, false};
-    if (copying)
+    if (copying && !(hold_flush_ && group_inputs_fresh_))
         for (int i = 0; i < 3; i++) {
             if (!ins[i]) continue;
             bool seen = false;
@@ -1090,6 +1098,7 @@ inline int DeviceSched::record_gate(void* stream, int op, bool copying, cufhe_am
         if (int rc = owner_->before_host_write(out, device_)) return fail(rc, "scheduler: flushing another device failed");
     for (int i = 0; i < 3; i++)
         if (need_up[i]) record_upload(ins[i], stream);
+    if (hold_flush_) group_inputs_fresh_ = true;
 
     uint32_t Din = base_depth_;       // the true data dependences: every input has been produced
     for (int i = 0; i < 3; i++)
@@ -1135,6 +1144,10 @@ inline int DeviceSched::record_gate(void* stream, int op, bool copying, cufhe_am
     } else if (D > Din || users) {
         hazard_by_level = true;
     }
+    // The result goes to out's tlwehost when this level's flush retires, and a recorded upload of out reads that memory when ITS level's
+    // flush is launched: the delivery must not land first.  Level order sees to that while the output waits for its buffer's readers; a
+    // renamed output (D = Din) can sit ahead of the upload, in an earlier flush (after_record launches a full front level by itself).
+    if (copying && po.last_upload >= base_depth_) D = std::max(D, po.last_upload);
     D = std::max(D, group_floor_);     // record_gate_group: every output of the evaluation in one level
 
     Plan& p = plan_at(D);
@@ -1222,7 +1235,8 @@ inline int DeviceSched::record_copy(void* stream, cufhe_amd_ctxt* c, bool to_dev
     }
     // CtxtCopyD2H, :201-207: the gather of a level runs after its gates
     if (int rc = owner_->before_host_write(c, device_)) return fail(rc, "scheduler: flushing another device failed");
-    const uint32_t D = std::max(base_depth_, pd.wdepth);
+    uint32_t D = std::max(base_depth_, pd.wdepth);
+    if (pd.last_upload >= base_depth_) D = std::max(D, pd.last_upload);      // as in record_gate: not ahead of a recorded upload out of the same tlwehost
     Plan& p = plan_at(D);
     if (home_copy_depth_ && D >= home_copy_depth_) p.level_ordered = true;          // a per-gate order fetches results BEFORE the copies home run
     add_dep(p, pd.wdepth);
