@@ -752,6 +752,49 @@ def gSpreadTRLWE(out, inp, stride, reps, st):
     trlwe_spread_batch(_ctxt_ptr(inp, dev), _ctxt_ptr(out, dev), 1, stride, reps, device=dev, stream=st.st())
 
 
+# ---- the recorded forms: scheduler nodes like the gates (they return at once; all of one dependence level share one launch sequence) ----
+LOOKUP_OP_BASE = 16384
+MAX_LOOKUPS = 64
+
+
+def DefineLookup(coeffs, offset=0, nout=1):
+    """A lookup definition: the address x = c0 in0 + c1 in1 + (0, .., 0, offset) formed inside the rotation, and the output count
+    (1, 2, 4 or 8).  Returns the op id for Lookup / gLookup (cufhe_amd_define_lookup)."""
+    c = (ctypes.c_int32 * 2)(int(coeffs[0]), int(coeffs[1]) if len(coeffs) > 1 else 0)
+    op = ctypes.c_int(-1)
+    check(lib.cufhe_amd_define_lookup(c, int(offset) & 0xFFFFFFFF, int(nout), ctypes.byref(op)))
+    return op.value
+
+
+def _lookup(op, copying, outs, table, in0, in1, st):
+    outs = list(outs)
+    arr = (ctypes.c_void_p * max(len(outs), 1))(*[None if o is None else o._h for o in outs])
+    check(lib.cufhe_amd_enqueue_lookup(st.device_id(), st.st(), int(op), 1 if copying else 0, len(outs), arr, table._h, in0._h,
+                                       in1._h if in1 is not None else None))
+
+
+def Lookup(outs, table, in0, in1, op, st):
+    """outs[j] <- output j of the lookup `op` (DefineLookup) of `table` (Trlwe) at the address formed from in0 and in1 (None for a
+    one-operand definition): recorded; operands from their host members, results delivered to the outputs' host members.  outs has the
+    definition's nout entries; None requests no output j (no key switch)."""
+    _lookup(op, True, outs, table, in0, in1, st)
+
+
+def gLookup(outs, table, in0, in1, op, st):
+    """Lookup on device buffers only, recorded like gNand."""
+    _lookup(op, False, outs, table, in0, in1, st)
+
+
+def gSpread(out, inp, stride, reps, st):
+    """out (Trlwe) <- Spread(inp, stride, reps), recorded (stride and reps powers of two, stride * reps <= N); out must not be inp."""
+    check(lib.cufhe_amd_enqueue_spread(st.device_id(), st.st(), 0, out._h, inp._h, int(stride), int(reps)))
+
+
+def gLutRotate(out, table, addr, st, nout=1):
+    """out (Trlwe) <- LutRotate(table, addr, log2 nout), recorded; out must not be table."""
+    check(lib.cufhe_amd_enqueue_lut_rotate(st.device_id(), st.st(), 0, int(nout), out._h, table._h, addr._h))
+
+
 def polymul512_batch(a, b, res, count, device=0, stream=None):
     check(lib.cufhe_amd_polymul512_batch(device, stream, count, a.ptr, b.ptr, res.ptr))
 

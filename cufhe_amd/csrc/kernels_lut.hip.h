@@ -1,6 +1,7 @@
 // kernels_lut.hip.h -- the keyless helper of the encrypted-table lookup:
 //
-//   trlwe_spread_kernel    Spread(c) = X^(-stride floor(reps/2)) sum_{i < reps} X^(i stride) c on both polynomials of a TRLWE
+//   trlwe_spread_kernel       Spread(c) = X^(-stride floor(reps/2)) sum_{i < reps} X^(i stride) c on both polynomials of a TRLWE
+//   trlwe_spread_desc_kernel  the same from descriptors: scattered buffers, a (stride, reps) of its own per TRLWE (the recorded form)
 //
 // (the lookup's rotations are blind_rotate_wave<true> / ll_rotate<true> / ll2_rotate<true>, kernels.hip.h and kernels_ll.hip.h).
 #pragma once
@@ -22,17 +23,13 @@ namespace cufhe_amd {
 // prefix array left in LDS (pre[q + 1] = Q at position q, pre[0] = 0) for the gathers of the windows.  No loop is `reps` long; all
 // arithmetic is uint32.  out must not overlap in (the host refuses it): other waves may still be loading.
 constexpr int kSpreadWavesPerBlock = 4;
-__global__ __launch_bounds__(64 * kSpreadWavesPerBlock) void trlwe_spread_kernel(uint32_t* __restrict__ out, const uint32_t* __restrict__ in,
-                                                                                 int polys, int stride, int reps)
+// The work of one wavefront on one polynomial: `coef` and `pre` are the wave's rows of the workgroup's LDS arrays, p / o the polynomial
+// read and written (ignored when !live: the wave then only keeps the workgroup's barriers).  stride and reps must be wave-uniform.
+__device__ __forceinline__ void trlwe_spread_wave(uint32_t* __restrict__ o, const uint32_t* __restrict__ p, bool live, int stride, int reps,
+                                                  uint32_t* __restrict__ coef, uint32_t* __restrict__ pre, int lane)
 {
-    __shared__ uint32_t coef[kSpreadWavesPerBlock][kN];
-    __shared__ uint32_t pre[kSpreadWavesPerBlock][kN + 1];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int poly = blockIdx.x * kSpreadWavesPerBlock + wave;
-    const bool live = poly < polys;
-    const uint32_t* p = in + (size_t)(live ? poly : 0) * kN;
 #pragma unroll
-    for (int r = 0; r < kRegs; r++) coef[wave][lane + 64 * r] = live ? p[lane + 64 * r] : 0u;
+    for (int r = 0; r < kRegs; r++) coef[lane + 64 * r] = live ? p[lane + 64 * r] : 0u;
     __syncthreads();
 
     const int len = kN / stride, big = kN - len * stride;      // classes rho < big have len + 1 members
@@ -44,24 +41,23 @@ __global__ __launch_bounds__(64 * kSpreadWavesPerBlock) void trlwe_spread_kernel
         const int q = 16 * lane + r;
         const int rho = q < split ? q / (len + 1) : big + (q - split) / len;
         const int t = q - class_start(rho);
-        run += coef[wave][rho + t * stride];
+        run += coef[rho + t * stride];
         v[r] = run;
     }
     uint32_t incl = run;                                        // inclusive wave scan of the lane totals
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_up(incl, d);
-        if (lane >= d) incl += o;
+        const uint32_t up = __shfl_up(incl, d);
+        if (lane >= d) incl += up;
     }
     const uint32_t carry = incl - run;
-    if (lane == 0) pre[wave][0] = 0u;
+    if (lane == 0) pre[0] = 0u;
 #pragma unroll
-    for (int r = 0; r < kRegs; r++) pre[wave][16 * lane + r + 1] = carry + v[r];
+    for (int r = 0; r < kRegs; r++) pre[16 * lane + r + 1] = carry + v[r];
     __syncthreads();
     if (!live) return;
 
     const int shift = stride * (reps / 2);
-    uint32_t* o = out + (size_t)poly * kN;
 #pragma unroll
     for (int r = 0; r < kRegs; r++) {
         const int k = lane + 64 * r;
@@ -69,18 +65,48 @@ __global__ __launch_bounds__(64 * kSpreadWavesPerBlock) void trlwe_spread_kernel
         const int m = neg ? k + shift - kN : k + shift;
         const int t = m / stride, rho = m - t * stride;
         const int start = class_start(rho), q = start + t;
-        uint32_t w = pre[wave][q + 1];
+        uint32_t w = pre[q + 1];
         if (t >= reps) {
-            w -= pre[wave][q + 1 - reps];
+            w -= pre[q + 1 - reps];
         } else {
-            w -= pre[wave][start];
+            w -= pre[start];
             const int jmax = kN - stride + rho;                 // the top member of the class of m + N
             const int tj = jmax / stride;
             const int qj = class_start(jmax - tj * stride) + tj;
-            w -= pre[wave][qj + 1] - pre[wave][qj + 1 - (reps - 1 - t)];
+            w -= pre[qj + 1] - pre[qj + 1 - (reps - 1 - t)];
         }
         o[k] = neg ? 0u - w : w;
     }
+}
+
+__global__ __launch_bounds__(64 * kSpreadWavesPerBlock) void trlwe_spread_kernel(uint32_t* __restrict__ out, const uint32_t* __restrict__ in,
+                                                                                 int polys, int stride, int reps)
+{
+    __shared__ uint32_t coef[kSpreadWavesPerBlock][kN];
+    __shared__ uint32_t pre[kSpreadWavesPerBlock][kN + 1];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int poly = blockIdx.x * kSpreadWavesPerBlock + wave;
+    const bool live = poly < polys;
+    trlwe_spread_wave(out + (size_t)(live ? poly : 0) * kN, in + (size_t)(live ? poly : 0) * kN, live, stride, reps, coef[wave], pre[wave], lane);
+}
+
+// The recorded form (cufhe_amd_enqueue_spread; lut.inc.h: lower_lut_ops): TRLWE g = polynomials 2g and 2g + 1 is read from d[g].in and
+// written to d[g].out with its OWN (stride, reps) -- recorded handles live in scattered buffers.  The wave index and the descriptor are
+// taken through readfirstlane, so the descriptor is a scalar load and len, big and split of the shared body stay in SGPRs as in the kernel
+// above.  d[g].out must not overlap any d[.].in of the launch (the scheduler never puts a writer of a buffer in the level of a reader).
+struct SpreadDesc { const uint32_t* in; uint32_t* out; int stride, reps; };
+__global__ __launch_bounds__(64 * kSpreadWavesPerBlock) void trlwe_spread_desc_kernel(const SpreadDesc* __restrict__ d, int polys)
+{
+    __shared__ uint32_t coef[kSpreadWavesPerBlock][kN];
+    __shared__ uint32_t pre[kSpreadWavesPerBlock][kN + 1];
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    const int poly = blockIdx.x * kSpreadWavesPerBlock + wave;
+    const bool live = poly < polys;
+    const SpreadDesc* e = d + ((live ? poly : 0) >> 1);
+    const int stride = live ? __builtin_amdgcn_readfirstlane(e->stride) : 1;
+    const int reps = live ? __builtin_amdgcn_readfirstlane(e->reps) : 1;
+    const size_t half = (size_t)(poly & 1) * kN;
+    trlwe_spread_wave(e->out + half, e->in + half, live, stride, reps, coef[wave], pre[wave], lane);
 }
 
 }  // namespace cufhe_amd

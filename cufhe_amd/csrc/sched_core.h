@@ -121,6 +121,9 @@ class Backend {
     // whether `op` is an output of a multi-output gate (several outputs of one evaluation share its rotation only when they sit in one
     // run_gates call): a flush that holds one is left to the level order, which keeps them together (compile_two_lane)
     virtual bool shares_rotation(int /*op*/) { return false; }
+    // which of the backend's lowerings `op` takes inside a run_gates call, 0 or 1 (0: the only one, the default): a backend that lowers
+    // some ops of a (level, kind) pair with a launch sequence of their own says so here, and Stats::launch_sequences counts both
+    virtual int lowering(int /*op*/) { return 0; }
     // the same as run_gates with the launch shape of a lane: 0 = chain, 1 = bulk (anything else: by the backend's own rules)
     virtual int run_gates_lane(int s, int level, const GateRef* g, size_t n, int /*lane*/) { return run_gates(s, level, g, n); }
     virtual int caller_stream_wait(void* /*caller_stream*/, void* /*ev*/) { return 0; }
@@ -211,7 +214,7 @@ struct Stats {
     uint64_t gates = 0;               // gates recorded
     uint64_t groups = 0;              // flushes handed to the device
     uint64_t levels = 0;              // dependence levels launched
-    uint64_t launch_sequences = 0;    // run_gates calls = (level, ciphertext kind) pairs with gates
+    uint64_t launch_sequences = 0;    // (level, ciphertext kind) pairs with gates, twice where the pair mixes the backend's two lowerings
     uint64_t uploads = 0, uploads_shared = 0, downloads = 0;
     uint64_t forced_syncs = 0;        // a stale `tlwehost` had to be waited for (see resolve_host)
     uint64_t max_level_gates = 0;
@@ -1106,6 +1109,9 @@ inline int DeviceSched::record_gate(void* stream, int op, bool copying, cufhe_am
     cufhe_amd_ctxt::PerDev& po = out->d[device_];
     uint32_t D = std::max(Din, po.ready);                             // write after write
     if (has_readers(po)) D = std::max(D, max_reader(po) + 1);         // write after read
+    // (These two lines, with Din above, are an invariant a backend may rely on: no operation of a level writes a buffer that ANOTHER
+    // operation of that level reads or writes -- a writer sits strictly behind them, or in a renamed buffer.  HipBackend::run_gates
+    // does: it completes the level's lookups, Spreads and table rotations, writes included, before the level's other gates read.)
     // operand buffers as of now: an in-place gate reads the buffer its output may be about to leave
     const uint32_t* const in_dev[3] = {ins[0]->d[device_].dev, ins[1] ? ins[1]->d[device_].dev : nullptr,
                                        ins[2] ? ins[2]->d[device_].dev : nullptr};
@@ -1350,8 +1356,11 @@ inline int DeviceSched::flush(size_t max_levels)
         ngates += p->gate_count();
         stats_.max_level_gates = std::max<uint64_t>(stats_.max_level_gates, p->gate_count());
         if (p->gate_count()) stats_.levels++;
-        for (int l = 0; l < kKinds; l++)
-            if (!p->gates[l].empty()) stats_.launch_sequences++;
+        for (int l = 0; l < kKinds; l++) {
+            bool seen[2] = {false, false};
+            for (const GateRef& gr : p->gates[l]) seen[be_->lowering(gr.op) != 0] = true;
+            stats_.launch_sequences += (uint64_t)seen[0] + (uint64_t)seen[1];
+        }
     }
     // dependences on levels that were launched earlier on another internal stream
     for (Plan* p : g->plans)

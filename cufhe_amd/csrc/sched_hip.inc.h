@@ -21,6 +21,15 @@ long g_sched_rename = 1;          // outputs take fresh device buffers instead o
 long g_sched_zero_copy = 1;       // 1: ciphertext staging is read / written by the scatter / gather kernels in pinned host memory (no copy-engine step)
 long g_sched_affinity = 1;        // 1: a device's launch worker runs on the CPUs local to that GPU (NUMA node of its PCI function)
 
+// The recorded lookups, Spreads and table rotations (lut.inc.h): their op ids are split off a level's gate list and lowered there
+constexpr int kMaxLookups = 64;
+struct LookupDef { int32_t c[2]; uint32_t off; int nout; int s; };      // x = c0 in0 + c1 in1 + (0, .., 0, off), nout = 2^s outputs
+bool is_lut_op(int op);
+bool is_spread_op(int op);
+const LookupDef* lookup_def(int op);      // of a lookup OUTPUT id (nullptr: none)
+int lower_lut_ops(DeviceState& s, hipStream_t st, const GateRef* g, size_t n);
+void lut_forget_definitions();
+
 // "0-15,128-143" -> CPU set; returns the number of CPUs parsed
 int parse_cpulist(const std::string& list, cpu_set_t* set)
 {
@@ -133,6 +142,20 @@ class HipBackend : public sched::Backend {
     {
         hipStream_t st;
         if (int rc = stream(s, &st)) return rc;
+        // recorded lookups, Spreads and table rotations go to lower_lut_ops as one launch sequence of their own, ahead of the level's
+        // other gates: no operation of a level writes a buffer that another one of the level reads or writes (sched_core.h: a writer
+        // sits strictly behind the readers and the writer of its buffer), so the two sequences may run in either order
+        size_t nlut = 0;
+        for (size_t i = 0; i < n; i++) nlut += is_lut_op(g[i].op) ? 1 : 0;
+        std::vector<sched::GateRef> lut, rest;
+        if (nlut) {
+            lut.reserve(nlut); rest.reserve(n - nlut);
+            for (size_t i = 0; i < n; i++) (is_lut_op(g[i].op) ? lut : rest).push_back(g[i]);
+            if (int rc = use_device(device_)) return keep(rc);
+            if (int rc = lower_lut_ops(g_dev[device_], st, lut.data(), lut.size())) return keep(rc);
+            if (rest.empty()) return 0;
+            g = rest.data(); n = rest.size();
+        }
         if (level == 2) return keep(run_trlwe_ops(device_, (void*)st, g, n));
         return keep(::run_gates(device_, (void*)st, level, n, [&](size_t i) { return g[i]; }));
     }
@@ -140,12 +163,18 @@ class HipBackend : public sched::Backend {
     // their own shapes.
     bool lane_model(LaneModel* m) override { return g_sched_two_lane && g_param_set < 0 && g_lvl0_ring == 1024 && plan::lane_model(cus(), m); }
     double launch_ms(size_t n) override { return plan::blind_rotate_ms(n, cus()); }
-    int gate_weight(int op) override { return op == CUFHE_AMD_MUX || op == CUFHE_AMD_NMUX ? 2 : op == CUFHE_AMD_NOT || op == CUFHE_AMD_COPY ? 0 : 1; }
+    int gate_weight(int op) override
+    {
+        if (is_spread_op(op)) return 0;       // (a lookup output and a table rotation: one rotation, like a gate)
+        return op == CUFHE_AMD_MUX || op == CUFHE_AMD_NMUX ? 2 : op == CUFHE_AMD_NOT || op == CUFHE_AMD_COPY ? 0 : 1;
+    }
     bool shares_rotation(int op) override
     {
+        if (const LookupDef* d = lookup_def(op)) return d->nout > 1;
         const UserGate* u = user_gate(op);
         return u && u->nout > 1;
     }
+    int lowering(int op) override { return is_lut_op(op) ? 1 : 0; }
     int run_gates_lane(int s, int level, const sched::GateRef* g, size_t n, int lane) override
     {
         g_br_shape = plan::lane_shape(lane, n, cus());
@@ -362,10 +391,11 @@ int sched_synchronize_all()
 
 // CleanUp: everything recorded completes, cached staging buffers and the internal streams go; the
 // scheduler itself (ciphertext slabs, workers) stays for the ciphertexts that outlive CleanUp.
-void sched_quiesce()
+void sched_quiesce(bool cleanup = true)
 {
+    if (g_scheduler) (void)g_scheduler->synchronize_all();
+    if (cleanup) lut_forget_definitions();     // lookup ids count from the last cufhe_amd_cleanup; whatever was recorded with them has run
     if (!g_scheduler) return;
-    (void)g_scheduler->synchronize_all();
     for (int d = 0; d < g_scheduler->gpu_num(); d++) {
         g_scheduler->dev(d).backend()->bind_thread();
         g_scheduler->dev(d).release_buffers();
@@ -378,7 +408,7 @@ void sched_quiesce()
 void sched_retire_generation()
 {
     if (!g_scheduler) return;
-    sched_quiesce();
+    sched_quiesce(false);
     if (g_scheduler->live_ctxts() == 0) delete g_scheduler;
     else g_parked.push_back(g_scheduler);
     g_scheduler = nullptr;

@@ -592,8 +592,9 @@ int cufhe_amd_pack_batch(int device, void* stream, size_t count_in, const uint32
  * 11; NULL: src[g] = g), rotation g reads tables[src[g]] and several rotations may name one table.  Refused before any device work: -1
  * for a null pointer (src excepted), nout not 1, 2, 4 or 8, src[g] outside [0, table_count), table_count = 0 with count > 0, an output
  * array overlapping tables, or "param_set" active; -3 without cufhe_amd_initialize.  Default parameter set only; the N = 2048 ring and
- * the parameter sets have none of this.  There is no recorded form (cufhe_amd_stream_fence orders a call behind the gates recorded on
- * its stream), no linear combination of several address ciphertexts inside the call (a user gate forms the address) and no key
+ * the parameter sets have none of this.  These batch calls are not recorded (cufhe_amd_stream_fence orders one behind the gates recorded
+ * on its stream) and take one address ciphertext per item; the recorded forms below -- cufhe_amd_enqueue_lookup, _enqueue_spread,
+ * _enqueue_lut_rotate -- are scheduler nodes, and a lookup definition forms the address from two ciphertexts inside the rotation.  No key
  * generation. */
 /* acc[count][2][N]: LutRotate after `steps` CMux steps (outside [0, n]: all n, as in cufhe_amd_blind_rotate_batch) */
 int cufhe_amd_lut_rotate_batch(int device, void* stream, size_t count, const uint32_t* tlwe0, const uint32_t* tables, size_t table_count,
@@ -608,6 +609,54 @@ int cufhe_amd_lut_lookup_batch(int device, void* stream, size_t count, const uin
  * top half box holding -values[0] included); values[j][m] at m N / p + j with stride = nout, reps = N / (p nout) gives
  * cufhe_amd_test_vector_multi.  -1: a null pointer, stride < 1, reps < 1, stride * reps > N, out overlapping in, "param_set" active. */
 int cufhe_amd_trlwe_spread_batch(int device, void* stream, size_t count, const uint32_t* in, int stride, int reps, uint32_t* out);
+
+/* ---- recorded forms of the above: lookups, Spread and the table rotation as scheduler nodes ----
+ * The three operations recorded like gates on ciphertext handles (cufhe_amd_ctxt_create: lvl0 ciphertexts of level 0, TRLWEs of level
+ * 2): every call returns at once, the scheduler orders it by its operands and all recorded lookups, rotations and Spreads of one
+ * dependence level are lowered together -- one rotation launch sequence, one key-switch launch, one Spread launch per level, whatever
+ * their number and whichever streams they were issued on.  Default parameter set only: with "param_set" active every entry returns -1
+ * and records nothing.
+ *
+ * A lookup DEFINITION is the linear part of the address and the output count: with x = c0 in0 + c1 in1 + (0, ..., 0, offset) mod 2^32
+ * on lvl0 ciphertexts (c0 != 0; in1 is used only when c1 != 0),
+ *     output j of Lookup(def, table, in0, in1) = LutLookup output j of (table, x, s = log2 nout),   0 <= j < nout,
+ * the sum formed inside the rotation (no bootstrap of its own).  Coefficients (1, 0) and offset 0 give the words of
+ * cufhe_amd_lut_lookup_batch.  Ids: CUFHE_AMD_LOOKUP_OP_BASE + k for the k-th definition since the last cufhe_amd_cleanup, k <
+ * CUFHE_AMD_MAX_LOOKUPS; output j of a definition is CUFHE_AMD_LOOKUP_OP_OUTPUT(op, j), so the range is 16384 .. 16895, above every
+ * other id range (lut.inc.h asserts it).  Definitions are immutable and hold no device data.  -1: c0 = 0, nout not 1, 2, 4 or 8, the
+ * 65th definition, a null pointer, "param_set" active; -3 before cufhe_amd_initialize.  The ids are ops of cufhe_amd_enqueue_lookup
+ * ONLY: cufhe_amd_gate, _gate_batch, _gate_list and _enqueue_gate refuse them as unknown ops. */
+#define CUFHE_AMD_LOOKUP_OP_BASE 16384
+#define CUFHE_AMD_MAX_LOOKUPS 64
+#define CUFHE_AMD_LOOKUP_OP_OUTPUT(op, j) ((op) + (j) * CUFHE_AMD_MAX_LOOKUPS)
+int cufhe_amd_define_lookup(const int32_t coeffs[2], uint32_t offset, int nout /* 1, 2, 4, 8 */, int* op);
+/* The nout outputs of ONE evaluation (one rotation), recorded as one group in one dependence level: outs[j] receives output j.  outs,
+ * in0, in1 have level 0, table level 2.  copying != 0: in0, in1 and table come from their host members, results go to the outputs' host
+ * members (visible after Synchronize / StreamQuery); 0: device buffers only.  nout = 1: the output may be an address operand (the rotation
+ * reads before the key switch writes); nout > 1: no output may be an operand.  outs[j] == NULL requests no output j: the evaluation
+ * costs its one rotation and one key switch per REQUESTED output, and several calls on the same (op, in0, in1, table) in one dependence
+ * level -- in any order of their outputs -- are still one rotation; at least one output must be requested.  -1, nothing recorded: op not a defined lookup (its
+ * output-0 id), nout not the definition's, wrong levels, in1 missing when c1 != 0, two outputs the same handle, a ciphertext created
+ * under another parameter set, "param_set" active, the N = 2048 ring ("lvl0_ring"); -3 without cufhe_amd_initialize. */
+int cufhe_amd_enqueue_lookup(int device, void* stream, int op, int copying, int nout, cufhe_amd_ctxt* const* outs,
+                             cufhe_amd_ctxt* table, cufhe_amd_ctxt* in0, cufhe_amd_ctxt* in1);
+/* Recorded Spread and recorded table rotation, operations of the TRLWE kind like CUFHE_AMD_TL_REFRESH.  Their ids carry their numbers:
+ * stride = 2^a, reps = 2^b, a + b <= 10 (every test-vector shape of cufhe_amd_test_vector[_multi]); other pairs stay on the batch call.
+ *     CUFHE_AMD_TL_SPREAD(a, b):   6400 .. 6560       CUFHE_AMD_TL_LUT_ROTATE(s), s = log2 nout:   6656 .. 6659
+ * (between CUFHE_AMD_TL_CMUX_ROTATE 4096 .. 6143 and the lvl2 user gates 8192 ..).
+ * enqueue_spread: out = Spread(in) on TRLWE handles; needs no key.  -1: out == in, stride or reps not a power of two, stride reps > N.
+ * enqueue_lut_rotate: out = LutRotate(table, addr, log2 nout) after all n steps; out and table of level 2, addr of level 0.  -1: out ==
+ * table, nout not 1, 2, 4 or 8; -3 without keys.
+ * Neither depends on "lvl0_ring": Spread has no key, and the rotation reads its lvl0 address with the N = 1024 key whichever ring the
+ * gates use (as cufhe_amd_lut_rotate_batch does); only the lookup, whose OUTPUTS are lvl0 ciphertexts of the gates' path, is refused there.
+ * The scheduler orders a writer strictly behind every recorded reader of its buffer and never renames TRLWE buffers, so out == in and
+ * out == table -- an operation reading the buffer it writes -- are the only aliasing rules. */
+#define CUFHE_AMD_TL_SPREAD_BASE 6400
+#define CUFHE_AMD_TL_SPREAD(a, b) (CUFHE_AMD_TL_SPREAD_BASE + 16 * (a) + (b))
+#define CUFHE_AMD_TL_LUT_ROTATE_BASE 6656
+#define CUFHE_AMD_TL_LUT_ROTATE(s) (CUFHE_AMD_TL_LUT_ROTATE_BASE + (s))        /* s = log2 nout, 0..3 */
+int cufhe_amd_enqueue_spread(int device, void* stream, int copying, cufhe_amd_ctxt* out, cufhe_amd_ctxt* in, int stride, int reps);
+int cufhe_amd_enqueue_lut_rotate(int device, void* stream, int copying, int nout, cufhe_amd_ctxt* out, cufhe_amd_ctxt* table, cufhe_amd_ctxt* addr);
 
 /* ---- other parameter sets (CMakeLists.txt:8-24: USE_80BIT_SECURITY / USE_CGGI19 / USE_CONCRETE select TFHEpp
  * parameter headers at build time; k > 1: src/bootstrap_gpu.cu:402-421; N = 512: include/ntt_gpu/ntt_gpuntt.cuh:283-329)

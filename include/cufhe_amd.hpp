@@ -649,8 +649,9 @@ inline void gPackTLWEs(cuFHETRLWElvl1& out, const std::vector<Ctxt<TFHEpp::lvl0p
 }
 /// Encrypted-table lookup (include/cufhe_amd.h, cufhe_amd_lut_lookup_batch): the blind rotation of the
 /// gates with a CIPHERTEXT as its table -- a TRLWE built on the device by gates, gPackTLWEs and gSpreadTRLWE is read by an encrypted
-/// index in one rotation.  All three are device-buffer forms and, like gPackTLWEs, not recorded: the stream is fenced first, so a call
-/// runs behind the gates recorded on `st` and what is recorded afterwards runs behind it.  Default parameter set only.
+/// index in one rotation.  These three are device-buffer forms and, like gPackTLWEs, BLOCKING: the stream is fenced first, so a call
+/// runs behind the gates recorded on `st` and what is recorded afterwards runs behind it.  The recorded forms are gLookup, gSpread and
+/// gLutRotate below.  Default parameter set only.
 /// out = Spread(in): X^(-stride floor(reps/2)) sum_{i < reps} X^(i stride) in -- entries at coefficients m N / p fill their boxes
 /// with stride 1, reps N / p.  out must not be in.
 inline void gSpreadTRLWE(cuFHETRLWElvl1& out, const cuFHETRLWElvl1& in, int stride, int reps, Stream st)
@@ -693,6 +694,49 @@ inline void gLookupTRLWE(const std::vector<Ctxt<TFHEpp::lvl0param>*>& outs, cons
     if (rc >= 0) rc = cufhe_amd_stream_synchronize(dev, st.raw());
     (void)cufhe_amd_free(dev, res);
     CUFHE_AMD_CHECK(rc);
+}
+
+/// The recorded forms of the three ("Recorded forms"): scheduler nodes like the gates.  They return at once,
+/// are ordered by their operands, and all lookups, Spreads and table rotations of one dependence level share one launch sequence.
+/// DefineLookup: the address x = c0 in0 + c1 in1 + (0, .., 0, offset) is formed inside the rotation; nout = 1, 2, 4 or 8 outputs.
+inline int DefineLookup(const std::array<int32_t, 2>& coeffs, uint32_t offset, int nout)
+{
+    int op = -1;
+    CUFHE_AMD_CHECK(cufhe_amd_define_lookup(coeffs.data(), offset, nout, &op));
+    return op;
+}
+namespace detail {
+inline void enqueue_lookup(int copying, const std::vector<Ctxt<TFHEpp::lvl0param>*>& outs, const cuFHETRLWElvl1& table,
+                           const Ctxt<TFHEpp::lvl0param>& in0, const Ctxt<TFHEpp::lvl0param>* in1, int op, Stream st)
+{
+    std::vector<cufhe_amd_ctxt*> hs(outs.size());
+    for (size_t j = 0; j < outs.size(); j++) hs[j] = outs[j] ? outs[j]->handle : nullptr;       // nullptr: output j is not requested
+    CUFHE_AMD_CHECK(cufhe_amd_enqueue_lookup(st.device_id(), st.raw(), op, copying, (int)hs.size(), hs.data(), table.handle, in0.handle,
+                                             in1 ? in1->handle : nullptr));
+}
+}  // namespace detail
+/// *outs[j] = output j of the lookup `op` of `table` at the address formed from in0 and in1 (nullptr for a one-operand definition);
+/// outs has the definition's nout entries, a nullptr entry requests no output j.
+/// Lookup: operands from their host members, results to the outputs' tlwehost after Synchronize(); gLookup: device buffers only.
+inline void Lookup(const std::vector<Ctxt<TFHEpp::lvl0param>*>& outs, const cuFHETRLWElvl1& table, const Ctxt<TFHEpp::lvl0param>& in0,
+                   const Ctxt<TFHEpp::lvl0param>* in1, int op, Stream st)
+{
+    detail::enqueue_lookup(1, outs, table, in0, in1, op, st);
+}
+inline void gLookup(const std::vector<Ctxt<TFHEpp::lvl0param>*>& outs, const cuFHETRLWElvl1& table, const Ctxt<TFHEpp::lvl0param>& in0,
+                    const Ctxt<TFHEpp::lvl0param>* in1, int op, Stream st)
+{
+    detail::enqueue_lookup(0, outs, table, in0, in1, op, st);
+}
+/// out = Spread(in), recorded: stride and reps powers of two, stride * reps <= N; out must not be in.
+inline void gSpread(cuFHETRLWElvl1& out, const cuFHETRLWElvl1& in, int stride, int reps, Stream st)
+{
+    CUFHE_AMD_CHECK(cufhe_amd_enqueue_spread(st.device_id(), st.raw(), 0, out.handle, in.handle, stride, reps));
+}
+/// out = LutRotate(table, addr, log2 nout), recorded; out must not be table.
+inline void gLutRotate(cuFHETRLWElvl1& out, const cuFHETRLWElvl1& table, const Ctxt<TFHEpp::lvl0param>& addr, Stream st, int nout = 1)
+{
+    CUFHE_AMD_CHECK(cufhe_amd_enqueue_lut_rotate(st.device_id(), st.raw(), 0, nout, out.handle, table.handle, addr.handle));
 }
 
 #undef CUFHE_AMD_GATE1
