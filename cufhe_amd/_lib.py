@@ -191,6 +191,7 @@ SIGNATURES = {
                                                   c_void]),
     "cufhe_amd_trlwe_spread_batch": (ctypes.c_int, [ctypes.c_int, c_void, ctypes.c_size_t, c_void, ctypes.c_int, ctypes.c_int, c_void]),
     "cufhe_amd_define_lookup": (ctypes.c_int, [c_i32p, ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
+    "cufhe_amd_enqueue_pack": (ctypes.c_int, [ctypes.c_int, c_void, ctypes.c_int, c_void, ctypes.c_size_t, c_void, c_void]),
     "cufhe_amd_enqueue_lookup": (ctypes.c_int, [ctypes.c_int, c_void, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void, c_void, c_void, c_void]),
     "cufhe_amd_enqueue_spread": (ctypes.c_int, [ctypes.c_int, c_void, ctypes.c_int, c_void, c_void, ctypes.c_int, ctypes.c_int]),
     "cufhe_amd_enqueue_lut_rotate": (ctypes.c_int, [ctypes.c_int, c_void, ctypes.c_int, ctypes.c_int, c_void, c_void, c_void]),

@@ -795,6 +795,31 @@ def gLutRotate(out, table, addr, st, nout=1):
     check(lib.cufhe_amd_enqueue_lut_rotate(st.device_id(), st.st(), 0, int(nout), out._h, table._h, addr._h))
 
 
+TL_PACK = 6912
+
+
+def _pack(copying, out_trlwe, ins, positions, st):
+    ins = list(ins)
+    count = len(ins)
+    assert count == len(positions)
+    arr = (ctypes.c_void_p * max(count, 1))(*[c._h for c in ins])
+    p = _i32(positions, count)
+    check(lib.cufhe_amd_enqueue_pack(st.device_id(), st.st(), 1 if copying else 0, out_trlwe._h, count, arr, _ptr(p)))
+
+
+def gPack(out_trlwe, ins, positions, st):
+    """out_trlwe (Trlwe) <- sum_m X^positions[m] PackKS(ins[m]), the words of gPackTLWEs, RECORDED: a scheduler node of len(ins) inputs
+    (1 .. N; handles and positions may repeat) on device buffers.  No fence, no gather, no wait; all packs of one dependence level
+    share one launch."""
+    _pack(False, out_trlwe, ins, positions, st)
+
+
+def Pack(out_trlwe, ins, positions, st):
+    """gPack with the inputs taken from their host members and the result delivered to out_trlwe's host words (after Synchronize /
+    StreamQuery)."""
+    _pack(True, out_trlwe, ins, positions, st)
+
+
 def polymul512_batch(a, b, res, count, device=0, stream=None):
     check(lib.cufhe_amd_polymul512_batch(device, stream, count, a.ptr, b.ptr, res.ptr))
 

@@ -101,4 +101,89 @@ __global__ __launch_bounds__(kPackThreads) void pack_keyswitch_kernel(
     }
 }
 
+// The recorded packs of one dependence level (pack.inc.h: lower_pack_ops) in one launch: the same workgroup over the CONCATENATION of
+// their terms, each term's operands named by a descriptor instead of in + m stride / out + dst 2N, so that inputs are read where the
+// gates left them and a tile may hold terms of several outputs.  Everything else is pack_keyswitch_kernel, which stays as it is (a
+// sibling, not a shared body: the batch kernel's code does not move).  A thread stages digits of ONE tile slot only (e % kPackTile is
+// tid % kPackTile for every e it visits), so it keeps that term's input pointer in a register: the gather has the batch kernel's lane
+// pattern, tile index fastest, one row per lane.
+struct PackDesc { const uint32_t* in; uint32_t* out; int32_t pos; };      // pos checked by the host: 0 <= pos < N
+
+// outs[count]: the level's distinct output TRLWEs, scattered; one workgroup zeroes one of them (rows are 16-byte aligned device slots)
+__global__ __launch_bounds__(kPackThreads) void pack_zero_desc_kernel(uint32_t* const* __restrict__ outs, int count)
+{
+    static_assert(kPackRowWords == 2 * 4 * kPackThreads, "two uint4 per thread");
+    if ((int)blockIdx.x >= count) return;
+    uint4* const row = reinterpret_cast<uint4*>(outs[blockIdx.x]);
+    row[threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);
+    row[kPackThreads + threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);
+}
+
+__global__ __launch_bounds__(kPackThreads) void pack_keyswitch_desc_kernel(
+    const PackDesc* __restrict__ terms, int count, const uint32_t* __restrict__ key, int tiles, int slices)
+{
+    static_assert(kPackThreads % kPackTile == 0, "a thread stages one tile slot");
+    __shared__ uint32_t rows[(kPackNumBase + 1) * kPackThreads];
+    __shared__ __attribute__((aligned(16))) uint8_t dig[kPackIBlock * kPackT * kPackTile];
+    const int tid = threadIdx.x;
+    const int c = blockIdx.x / tiles, tile = blockIdx.x % tiles;
+    const int slice = blockIdx.y;
+    const int t0 = (int)plan::pack_tile_first(tile, kPackTile);
+    const int nt = plan::pack_tile_inputs(tile, kPackTile, count);
+    const int i_begin = plan::pack_slice_begin(slice, slices, kLvl0N), i_end = plan::pack_slice_begin(slice + 1, slices, kLvl0N);
+
+    uint32_t acc[kPackTile];
+#pragma unroll
+    for (int t = 0; t < kPackTile; t++) acc[t] = 0u;
+    rows[tid] = 0u;
+    uint32_t* const col = rows + tid;
+    const uint32_t* kbase = key + c * kPackThreads + tid;
+    const int ts = tid % kPackTile;                // the tile slot this thread stages
+    const uint32_t* const staged = ts < nt ? terms[t0 + ts].in : nullptr;
+
+    for (int ib = i_begin; ib < i_end; ib += kPackIBlock) {
+        const int ni = min(kPackIBlock, i_end - ib);
+        __syncthreads();                   // the digits of the previous block have been read
+        for (int ii = tid / kPackTile; ii < ni; ii += kPackThreads / kPackTile) {
+            const uint32_t a = staged ? staged[ib + ii] + kPackRound : 0u;
+#pragma unroll
+            for (int j = 0; j < kPackT; j++) dig[(ii * kPackT + j) * kPackTile + ts] = (uint8_t)((a >> (32 - kPackBasebit * (j + 1))) & kPackNumBase);
+        }
+        __syncthreads();
+        for (int ii = 0; ii < ni; ii++) {
+            const uint32_t* krow_i = kbase + (size_t)(ib + ii) * kPackT * kPackNumBase * kPackRowWords;
+            for (int j = 0; j < kPackT; j++) {
+                const uint32_t* krow = krow_i + (size_t)j * kPackNumBase * kPackRowWords;
+                uint32_t v[kPackNumBase];
+#pragma unroll
+                for (int k = 0; k < kPackNumBase; k++) v[k] = krow[k * kPackRowWords];
+#pragma unroll
+                for (int k = 0; k < kPackNumBase; k++) col[(k + 1) * kPackThreads] = v[k];     // this thread's column only: no barrier
+                const uint32_t* dg = (const uint32_t*)(dig + (ii * kPackT + j) * kPackTile);
+#pragma unroll
+                for (int q = 0; q < kPackTile / 4; q++) {
+                    if (4 * q < nt) {              // uniform
+                        const uint32_t w = dg[q];  // the same address in every lane: a broadcast
+#pragma unroll
+                        for (int b = 0; b < 4; b++) acc[4 * q + b] += col[((w >> (8 * b)) & 0xffu) * kPackThreads];
+                    }
+                }
+            }
+        }
+    }
+    const int e = c * kPackThreads + tid;          // row word: polynomial e / N, coefficient e % N
+    const int poly = e / kN, k = e % kN;
+    const bool holds_b = slice == 0 && e == kN;
+#pragma unroll
+    for (int t = 0; t < kPackTile; t++) {
+        if (t >= nt) continue;
+        const PackDesc d = terms[t0 + t];          // uniform: the same descriptor in every lane
+        uint32_t val = 0u - acc[t];
+        if (holds_b) val += d.in[kLvl0N];
+        const int kk = k + d.pos;
+        if (kk >= kN) val = 0u - val;
+        atomicAdd(d.out + poly * kN + (kk & (kN - 1)), val);
+    }
+}
+
 }  // namespace cufhe_amd

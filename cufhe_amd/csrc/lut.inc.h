@@ -78,6 +78,11 @@ static_assert(id_ranges_apart(CUFHE_AMD_TL_SPREAD_BASE, kSpreadOpEnd, CUFHE_AMD_
                   id_ranges_apart(CUFHE_AMD_TL_SPREAD_BASE, kSpreadOpEnd, CUFHE_AMD_LOOKUP_OP_BASE, kLookupOpEnd) &&
                   id_ranges_apart(CUFHE_AMD_TL_LUT_ROTATE_BASE, kLutRotateOpEnd, CUFHE_AMD_LOOKUP_OP_BASE, kLookupOpEnd),
               "the three new ranges do not overlap one another");
+static_assert(apart_from_existing(CUFHE_AMD_TL_PACK, CUFHE_AMD_TL_PACK + 1) &&
+                  id_ranges_apart(CUFHE_AMD_TL_PACK, CUFHE_AMD_TL_PACK + 1, CUFHE_AMD_TL_SPREAD_BASE, kSpreadOpEnd) &&
+                  id_ranges_apart(CUFHE_AMD_TL_PACK, CUFHE_AMD_TL_PACK + 1, CUFHE_AMD_TL_LUT_ROTATE_BASE, kLutRotateOpEnd) &&
+                  id_ranges_apart(CUFHE_AMD_TL_PACK, CUFHE_AMD_TL_PACK + 1, CUFHE_AMD_LOOKUP_OP_BASE, kLookupOpEnd),
+              "the recorded pack's id (pack.inc.h) overlaps no other op id");
 
 LookupDef g_lookup[kMaxLookups];
 std::atomic<int> g_lookup_count{0};      // published with release once the entry is written (definitions are immutable)

@@ -1,11 +1,52 @@
 // pack.inc.h -- host side of TLWE packing (included by capi.hip): lvl0 TLWEs -> coefficients of lvl1
 // TRLWEs by pack_keyswitch_kernel (kernels_pack.hip.h) in the shape of plan::plan_pack (launch_plan.h).  The packing key is the
-// caller's (cufhe_amd_pack_initialize); default parameter set only.  There is no recorded form: callers order the call behind gates
-// recorded on a stream with cufhe_amd_stream_fence.
+// caller's (cufhe_amd_pack_initialize); default parameter set only.  Two forms: cufhe_amd_pack_batch on raw device arrays, which callers
+// order behind gates recorded on a stream with cufhe_amd_stream_fence, and the recorded cufhe_amd_enqueue_pack on ciphertext handles, a
+// scheduler node of n inputs (DeviceSched::record_pack); all recorded packs of a dependence level are lowered together by
+// lower_pack_ops: one zeroing launch and one launch of pack_keyswitch_desc_kernel over the concatenation of their terms.
 
 namespace {
 
 int fail_pack_set() { return fail(-1, "TLWE packing runs on the default path only: not with \"param_set\" active"); }
+
+// The recorded packs of ONE dependence level.  Their outputs are distinct buffers (a second writer of a buffer sits in a later level)
+// that nothing else of the level touches, so they are zeroed through a pointer table and every term of every pack adds into them from
+// one launch in the shape plan_pack gives for the total: a tile of 64 terms may straddle outputs.  Descriptors live in the stream's
+// workspace from offset 0, like every lowering's (HipBackend::run_gates runs this as a launch sequence of its own).
+int lower_pack_ops(DeviceState& s, hipStream_t st, const GateRef* g, size_t n)
+{
+    if (n == 0) return 0;
+    if (g_param_set >= 0) return fail_pack_set();
+    if (!s.pack_key) return fail(-3, "cufhe_amd_pack_initialize has not been called for this device");
+    std::vector<uint32_t*> outs;
+    std::vector<PackDesc> terms;
+    outs.reserve(n);
+    for (size_t i = 0; i < n; i++) {
+        const sched::PackNode* node = sched::pack_node(g[i]);
+        if (g[i].op != CUFHE_AMD_TL_PACK || !g[i].out || !node || node->terms.empty()) return fail(-1, "internal: not a recorded pack");
+        outs.push_back(g[i].out);
+        for (const sched::PackTerm& t : node->terms) {
+            if (!t.in || t.pos < 0 || t.pos >= kN) return fail(-1, "internal: recorded pack term out of range");
+            terms.push_back({t.in, g[i].out, t.pos});
+        }
+    }
+    if (terms.size() > (size_t)INT32_MAX / 2) return fail(-1, "recorded packs: the terms of one level exceed the kernel's index type");
+    ProfScope prof{s, st, terms.size(), true};       // as in the batch call: zeroing, staging of the descriptors and the kernel, one launcher call
+    if (int rc = prof.begin()) return rc;
+    Scratch sc;
+    if (int rc = open_scratch(s, st, terms.size() * sizeof(PackDesc) + outs.size() * sizeof(uint32_t*) + 8192, &sc)) return rc;
+    uint32_t** douts;
+    PackDesc* dterms;
+    if (int rc = upload_descs(s, sc, outs, &douts)) return rc;
+    if (int rc = upload_descs(s, sc, terms, &dterms)) return rc;
+    hipLaunchKernelGGL(pack_zero_desc_kernel, dim3((unsigned)outs.size()), dim3(kPackThreads), 0, st, douts, (int)outs.size());
+    HIP_TRY(hipGetLastError());
+    const plan::PackPlan p = plan::plan_pack(terms.size(), cus_of(s), kPackGeometry, g_tuning);
+    hipLaunchKernelGGL(pack_keyswitch_desc_kernel, dim3(p.grid_x, p.grid_y), dim3(kPackThreads), 0, st, dterms, (int)terms.size(), s.pack_key,
+                       p.tiles, p.slices);
+    HIP_TRY(hipGetLastError());
+    return prof.commit();
+}
 
 }  // namespace
 
@@ -85,6 +126,30 @@ int cufhe_amd_pack_batch(int device, void* stream, size_t count_in, const uint32
                        trlwe, p.tiles, p.slices);
     HIP_TRY(hipGetLastError());
     return prof.commit();
+}
+
+int cufhe_amd_enqueue_pack(int device, void* stream, int copying, cufhe_amd_ctxt* out, size_t count_in, cufhe_amd_ctxt* const* ins,
+                           const int32_t* pos)
+{
+    std::lock_guard<std::mutex> lk(g_sched_mu);
+    if (g_param_set >= 0) return fail_pack_set();
+    if (int rc = check_device(device)) return rc;
+    if (!out || !ins || !pos) return fail(-1, "enqueue_pack: null pointer");
+    if (count_in < 1 || count_in > (size_t)kN) return fail(-1, "enqueue_pack: count_in outside [1, N]");
+    for (size_t m = 0; m < count_in; m++) {
+        if (!ins[m]) return fail(-1, "enqueue_pack: null ciphertext");
+        if (pos[m] < 0 || pos[m] >= kN) return fail(-1, "enqueue_pack: pos outside [0, N)");
+    }
+    if (out->level != 2) return fail(-1, "enqueue_pack: out is a TRLWE (level 2), the inputs lvl0 ciphertexts (level 0)");
+    for (size_t m = 0; m < count_in; m++)
+        if (ins[m]->level != 0) return fail(-1, "enqueue_pack: out is a TRLWE (level 2), the inputs lvl0 ciphertexts (level 0)");
+    sched::Scheduler* S = scheduler();
+    if (int rc = sched_check_ctxt(S, out)) return rc;
+    for (size_t m = 0; m < count_in; m++)
+        if (int rc = sched_check_ctxt(S, ins[m])) return rc;
+    if (!g_dev[device].pack_key) return fail(-3, "cufhe_amd_pack_initialize has not been called for this device");
+    if (int rc = S->dev(device).record_pack(stream, CUFHE_AMD_TL_PACK, copying != 0, out, ins, pos, count_in)) return sched_error(S->dev(device), rc);
+    return 0;
 }
 
 }  // extern "C"

@@ -65,6 +65,12 @@ constexpr int kKinds = 3;
 // cuFHETRGSWNTTlvl1, include/cufhe_gpu.cuh:136-146), which is only ever an INPUT (of CMUXNTT, a kind-2 operation).
 constexpr int kLevels = 4;
 struct CopyRec { uint32_t* dev; size_t slot; int level; };      // staging word offset <-> a ciphertext's device buffer
+// A node of variable arity (DeviceSched::record_pack): out = sum over its terms of X^pos * f(in), every `in` a level-0 device buffer as
+// it stood when the node was recorded.  The node's GateRef carries a pointer to this in in0 (in1, in2 null); the storage belongs to the
+// node's Plan and keeps its address until the level retires.
+struct PackTerm { const uint32_t* in; int32_t pos; };
+struct PackNode { std::vector<PackTerm> terms; };
+inline const PackNode* pack_node(const GateRef& g) { return reinterpret_cast<const PackNode*>(g.in0); }
 
 // The device layer of ONE device.  Every method returns 0 or a negative status (text through
 // error_text()).  `s` is the index of one of the backend's internal streams; work submitted to one
@@ -271,6 +277,7 @@ struct Plan {                         // one dependence level of the recorded pr
     std::vector<CopyRec> uploads, downloads;
     std::vector<cufhe_amd_ctxt*> upload_ctxts;     // parallel to uploads
     std::vector<Delivery> deliveries;              // parallel to downloads
+    std::deque<PackNode> packs;                    // the term lists of this level's packs (a deque: a node never moves)
     size_t in_words = 0;                           // staging words of the uploads (filled by the launch thread)
     size_t out_words = 0;
     std::vector<uint32_t> dep_depths;              // earlier levels this one must follow
@@ -281,6 +288,7 @@ struct Plan {                         // one dependence level of the recorded pr
     {
         gates[0].clear(); gates[1].clear(); gates[2].clear(); uploads.clear(); downloads.clear(); upload_ctxts.clear(); deliveries.clear();
         deps[0].clear(); deps[1].clear(); deps[2].clear();
+        packs.clear();
         level_ordered = false;
         dep_depths.clear(); streams.clear();
         in_words = out_words = in_base = out_base = 0;
@@ -443,6 +451,10 @@ class DeviceSched {
     // call holds all of them and the backend evaluates them once.  The caller has checked that no output is an input and that the
     // outputs are distinct handles.
     int record_gate_group(void* stream, const int* ops, bool copying, cufhe_amd_ctxt* const* outs, size_t n, cufhe_amd_ctxt* const (&ins)[3]);
+    // A pack: one kind-2 writer of `out` (level 2) that reads n >= 1 level-0 inputs, out = sum_m X^pos[m] f(ins[m]).  A handle may
+    // appear several times.  Every input is a reader at the node's level exactly as a gate's operand is: a later write of one is renamed
+    // or waits, a destroyed one lives until the level retires.  The node's GateRef carries its PackNode (pack_node()).
+    int record_pack(void* stream, int op, bool copying, cufhe_amd_ctxt* out, cufhe_amd_ctxt* const* ins, const int32_t* pos, size_t n);
     int record_copy(void* stream, cufhe_amd_ctxt* c, bool to_device);
     int flush(size_t max_levels = (size_t)-1);
     int flush_for_completion()                 // the caller is about to wait for everything: renamed values go home in the same flush
@@ -1227,6 +1239,55 @@ inline int DeviceSched::record_gate(void* stream, int op, bool copying, cufhe_am
     pending_gates_++;
     stats_.gates++;
     return hold_flush_ ? 0 : after_record();
+}
+
+// record_gate does the work for the output and the first three inputs -- the write hazards on `out`, the delivery of a copying pack, the
+// flush rules -- with the node's level raised to what the LATEST of all n inputs allows (group_floor_); the inputs beyond the third
+// are then entered at the level the node received.  No flush in between (hold_flush_): the level must still be on record.
+inline int DeviceSched::record_pack(void* stream, int op, bool copying, cufhe_amd_ctxt* out, cufhe_amd_ctxt* const* ins, const int32_t* pos,
+                                    size_t n)
+{
+    if (n == 0 || out->level != 2) return fail(-1, "pack: at least one input, a TRLWE output");
+    if (copying) {
+        // every distinct input once, as record_gate does for its operands: all may-wait resolutions first, then the uploads
+        std::vector<cufhe_amd_ctxt*> fresh;
+        std::unordered_set<cufhe_amd_ctxt*> seen;
+        for (size_t m = 0; m < n; m++) {
+            if (!seen.insert(ins[m]).second) continue;
+            if (!ins[m]->host) return fail(-1, "pack of a destroyed ciphertext");
+            bool need = false;
+            if (int rc = resolve_host(ins[m], &need, stream)) return rc;
+            if (need) fresh.push_back(ins[m]);
+        }
+        for (cufhe_amd_ctxt* c : fresh) record_upload(c, stream);
+    }
+    uint32_t latest = 0;
+    for (size_t m = 0; m < n; m++) latest = std::max(latest, ins[m]->d[device_].ready);
+    cufhe_amd_ctxt* const first[3] = {ins[0], n > 1 ? ins[1] : nullptr, n > 2 ? ins[2] : nullptr};
+    group_floor_ = latest;
+    hold_flush_ = true;
+    group_inputs_fresh_ = true;          // (the operands have just been resolved above)
+    const int rc = record_gate(stream, op, copying, out, first, 2);
+    group_floor_ = 0;
+    hold_flush_ = false;
+    group_inputs_fresh_ = false;
+    if (rc) return rc;
+    cufhe_amd_ctxt::PerDev& po = out->d[device_];
+    const uint32_t L = po.wdepth;
+    Plan& p = plan_at(L);
+    p.level_ordered = true;              // a TRLWE output is never renamed: the flush stays in level order
+    p.packs.emplace_back();
+    PackNode& node = p.packs.back();
+    node.terms.reserve(n);
+    for (size_t m = 0; m < n; m++) node.terms.push_back({ins[m]->d[device_].dev, pos[m]});
+    for (size_t m = 3; m < n; m++) {
+        cufhe_amd_ctxt::PerDev& pd = ins[m]->d[device_];
+        add_dep(p, pd.wdepth);
+        add_reader(pd, L);               // a later write of this input follows the pack, or takes a fresh buffer
+        use(pd, L);                      // a destroyed input keeps its buffer until the pack has run
+    }
+    p.gates[2][po.widx] = GateRef{op, po.dev, reinterpret_cast<const uint32_t*>(&node), nullptr, nullptr};
+    return after_record();
 }
 
 inline int DeviceSched::record_copy(void* stream, cufhe_amd_ctxt* c, bool to_device)

@@ -29,6 +29,9 @@ bool is_spread_op(int op);
 const LookupDef* lookup_def(int op);      // of a lookup OUTPUT id (nullptr: none)
 int lower_lut_ops(DeviceState& s, hipStream_t st, const GateRef* g, size_t n);
 void lut_forget_definitions();
+// The recorded packs (pack.inc.h): split off a level's TRLWE-kind list in the same way
+int lower_pack_ops(DeviceState& s, hipStream_t st, const GateRef* g, size_t n);
+bool is_split_op(int op) { return op == CUFHE_AMD_TL_PACK || is_lut_op(op); }
 
 // "0-15,128-143" -> CPU set; returns the number of CPUs parsed
 int parse_cpulist(const std::string& list, cpu_set_t* set)
@@ -145,14 +148,16 @@ class HipBackend : public sched::Backend {
         // recorded lookups, Spreads and table rotations go to lower_lut_ops as one launch sequence of their own, ahead of the level's
         // other gates: no operation of a level writes a buffer that another one of the level reads or writes (sched_core.h: a writer
         // sits strictly behind the readers and the writer of its buffer), so the two sequences may run in either order
-        size_t nlut = 0;
-        for (size_t i = 0; i < n; i++) nlut += is_lut_op(g[i].op) ? 1 : 0;
-        std::vector<sched::GateRef> lut, rest;
-        if (nlut) {
-            lut.reserve(nlut); rest.reserve(n - nlut);
-            for (size_t i = 0; i < n; i++) (is_lut_op(g[i].op) ? lut : rest).push_back(g[i]);
+        // (recorded packs likewise, all of the level in lower_pack_ops)
+        size_t nsplit = 0;
+        for (size_t i = 0; i < n; i++) nsplit += is_split_op(g[i].op) ? 1 : 0;
+        std::vector<sched::GateRef> lut, pack, rest;
+        if (nsplit) {
+            rest.reserve(n - nsplit);
+            for (size_t i = 0; i < n; i++) (g[i].op == CUFHE_AMD_TL_PACK ? pack : is_lut_op(g[i].op) ? lut : rest).push_back(g[i]);
             if (int rc = use_device(device_)) return keep(rc);
             if (int rc = lower_lut_ops(g_dev[device_], st, lut.data(), lut.size())) return keep(rc);
+            if (int rc = lower_pack_ops(g_dev[device_], st, pack.data(), pack.size())) return keep(rc);
             if (rest.empty()) return 0;
             g = rest.data(); n = rest.size();
         }
@@ -165,7 +170,7 @@ class HipBackend : public sched::Backend {
     double launch_ms(size_t n) override { return plan::blind_rotate_ms(n, cus()); }
     int gate_weight(int op) override
     {
-        if (is_spread_op(op)) return 0;       // (a lookup output and a table rotation: one rotation, like a gate)
+        if (is_spread_op(op) || op == CUFHE_AMD_TL_PACK) return 0;       // (a lookup output and a table rotation: one rotation, like a gate)
         return op == CUFHE_AMD_MUX || op == CUFHE_AMD_NMUX ? 2 : op == CUFHE_AMD_NOT || op == CUFHE_AMD_COPY ? 0 : 1;
     }
     bool shares_rotation(int op) override
@@ -174,7 +179,7 @@ class HipBackend : public sched::Backend {
         const UserGate* u = user_gate(op);
         return u && u->nout > 1;
     }
-    int lowering(int op) override { return is_lut_op(op) ? 1 : 0; }
+    int lowering(int op) override { return is_split_op(op) ? 1 : 0; }
     int run_gates_lane(int s, int level, const sched::GateRef* g, size_t n, int lane) override
     {
         g_br_shape = plan::lane_shape(lane, n, cus());

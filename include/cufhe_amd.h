@@ -560,8 +560,9 @@ int cufhe_amd_circuit_bootstrap_batch(int device, void* stream, size_t count, co
  * An output no input names is the zero TRLWE; inputs at the same position of the same output add; all count_out outputs are written.
  * K is the caller's key, [n][t][2^basebit - 1][k+1][N] uint32 (30 965 760 words, 123.9 MB, on every device of SetGPUNum):
  * K[i][j][v-1] = TRLWE_s1(v * s0_i * 2^(32 - 2 (j+1))), a constant message, phase b - a s.  The library does not generate it.
- * Default parameter set only ("param_set" active: -1).  There is no recorded form: cufhe_amd_stream_fence orders a call behind the
- * gates recorded on its stream. */
+ * Default parameter set only ("param_set" active: -1).  cufhe_amd_pack_batch works on raw device arrays and is not recorded
+ * (cufhe_amd_stream_fence orders a call behind the gates recorded on its stream); cufhe_amd_enqueue_pack below is the recorded form on
+ * ciphertext handles. */
 typedef struct cufhe_amd_pack_params {
     uint32_t n, N;                     /* input lvl0 dimension, output ring */
     uint32_t t, basebit;               /* 8 unsigned digits of 2 bits */
@@ -577,6 +578,21 @@ int cufhe_amd_pack_initialize(const uint32_t* key, size_t words);
  * by the rule of plan_pack) forces the number of slices the lvl0 words are cut into; the words do not depend on the shape. */
 int cufhe_amd_pack_batch(int device, void* stream, size_t count_in, const uint32_t* tlwe0, const int32_t* dst, const int32_t* pos,
                          size_t count_out, uint32_t* trlwe);
+/* The recorded form: a scheduler node of count_in inputs, an operation of the TRLWE kind like CUFHE_AMD_TL_REFRESH with the single id
+ * CUFHE_AMD_TL_PACK (between CUFHE_AMD_TL_LUT_ROTATE 6656 .. 6659 and the lvl2 user gates 8192 ..).
+ *     out = sum_m X^pos[m] PackKS(ins[m]),   0 <= m < count_in
+ * word for word what cufhe_amd_pack_batch gives with count_out = 1 and dst all 0.  out is a TRLWE handle (level 2), every ins[m] a lvl0
+ * handle (level 0), 1 <= count_in <= N; a handle may appear several times and positions may repeat (the terms add).  The call returns
+ * at once; the scheduler orders the node behind the producers of ALL its inputs and behind the readers and the writer of out, a later
+ * gate that overwrites an input is renamed or placed behind the node, and all recorded packs of one dependence level are lowered
+ * together: one zeroing launch and one key-switch launch over the concatenation of their terms, reading the inputs where they lie
+ * ("pack_slices" and "cus_override" as above).  copying != 0: the inputs come from their host members, the result goes to out's host
+ * words (visible after Synchronize / StreamQuery); 0: device buffers only.  ins and pos are read during the call.  -1, nothing recorded:
+ * a null pointer, count_in outside [1, N], pos[m] outside [0, N), wrong levels, a destroyed input, a ciphertext created under another
+ * parameter set, "param_set" active; -3 when this device has no packing key.  Independent of "lvl0_ring". */
+#define CUFHE_AMD_TL_PACK 6912
+int cufhe_amd_enqueue_pack(int device, void* stream, int copying, cufhe_amd_ctxt* out, size_t count_in, cufhe_amd_ctxt* const* ins,
+                           const int32_t* pos);
 
 /* ---- encrypted-table lookup: blind rotation from a caller's TRLWE (no counterpart in the reference) ----
  * The blind rotation of the gates reads a PLAINTEXT table: its accumulator starts as (0, X^bbar TV).  Here it starts from a ciphertext:

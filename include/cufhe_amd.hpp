@@ -738,6 +738,28 @@ inline void gLutRotate(cuFHETRLWElvl1& out, const cuFHETRLWElvl1& table, const C
 {
     CUFHE_AMD_CHECK(cufhe_amd_enqueue_lut_rotate(st.device_id(), st.raw(), 0, nout, out.handle, table.handle, addr.handle));
 }
+/// The recorded form of gPackTLWEs: out = sum_m X^pos[m] PackKS(*ins[m]), the same words, as a scheduler node
+/// of ins.size() inputs (1 .. N; handles and positions may repeat).  No fence, no gather, no wait: the call returns at once and all
+/// packs of one dependence level share one launch.  Pack: inputs from their host members, the result to out.trlwehost after
+/// Synchronize(); gPack: device buffers only.
+namespace detail {
+inline void enqueue_pack(int copying, cuFHETRLWElvl1& out, const std::vector<Ctxt<TFHEpp::lvl0param>*>& ins, const std::vector<int>& pos, Stream st)
+{
+    if (ins.size() != pos.size()) CUFHE_AMD_CHECK(-1);
+    std::vector<cufhe_amd_ctxt*> hs(ins.size());
+    for (size_t m = 0; m < ins.size(); m++) hs[m] = ins[m] ? ins[m]->handle : nullptr;
+    const std::vector<int32_t> p(pos.begin(), pos.end());
+    CUFHE_AMD_CHECK(cufhe_amd_enqueue_pack(st.device_id(), st.raw(), copying, out.handle, hs.size(), hs.data(), p.data()));
+}
+}  // namespace detail
+inline void Pack(cuFHETRLWElvl1& out, const std::vector<Ctxt<TFHEpp::lvl0param>*>& ins, const std::vector<int>& pos, Stream st)
+{
+    detail::enqueue_pack(1, out, ins, pos, st);
+}
+inline void gPack(cuFHETRLWElvl1& out, const std::vector<Ctxt<TFHEpp::lvl0param>*>& ins, const std::vector<int>& pos, Stream st)
+{
+    detail::enqueue_pack(0, out, ins, pos, st);
+}
 
 #undef CUFHE_AMD_GATE1
 #undef CUFHE_AMD_GATE2
