@@ -22,6 +22,7 @@
 #include "../../include/cufhe_amd.h"
 #include "sched_core.h"
 #include "launch_plan.h"
+#include "op_registry.h"
 #include "kernels.hip.h"
 #include "kernels_lvl2.hip.h"
 #include "kernels_lvl2q.hip.h"
@@ -501,126 +502,20 @@ const int kGateTab[10][3] = {
 
 using sched::GateRef;
 
-// User gates (cufhe_amd_define_gate): definition k is op CUFHE_AMD_USER_OP_BASE + k.  A definition is written once, before
-// g_user_count is raised past it, and never changes afterwards, so the gate paths read it without a lock; its test vector is row k
-// of every device's DeviceState::tvs.  CleanUp drops them all.
-// A multi-output definition (cufhe_amd_define_gate_multi) has nout = 2^s > 1 outputs: output j of definition k is op
-// CUFHE_AMD_USER_OP_OUTPUT(base + k, j) = base + k + j * CUFHE_AMD_MAX_USER_GATES, and its rotations carry s beside the row
-// (make_pad).  A single-output definition has nout = 1, s = 0.
-struct UserGate { int32_t c[3]; uint32_t off; bool tv; int nout; int s; };
-static_assert(CUFHE_AMD_MAX_USER_GATES == kMaxUserGates, "the header's capacity is the device table's");
-static_assert(CUFHE_AMD_USER_OP_BASE > CUFHE_AMD_TL_CMUX, "user op ids do not overlap the built-in or TRLWE-level ops");
-static_assert(CUFHE_AMD_USER_OP_OUTPUT(CUFHE_AMD_USER_OP_BASE + kMaxUserGates - 1, (1 << kMaxOutputShift) - 1) ==
-                  CUFHE_AMD_USER_OP_BASE + (kMaxUserGates << kMaxOutputShift) - 1, "output ids fill [base, base + 8 * 64)");
-UserGate g_user[kMaxUserGates];
-std::atomic<int> g_user_count{0};
-bool is_user_op(int op) { return op >= CUFHE_AMD_USER_OP_BASE && op < CUFHE_AMD_USER_OP_BASE + (kMaxUserGates << kMaxOutputShift); }
+// The op ids a caller defines (user gates of the three paths, lookups): ranges, tables and the rule of where an id runs are
+// op_registry.h's.  The test vector of definition k is row k of every device's table: DeviceState::tvs, ::tvs2 (64-bit, lvl2.inc.h), or
+// PsState::tvs of the set the definition was made for (N words of that set, paramsets.inc.h).  CleanUp drops the definitions.
+using opreg::UserGate;
+using opreg::user_gate_arity;
+opreg::Registry g_ops;
+static_assert(opreg::kUserOps.cap == kMaxUserGates && opreg::kPsUserOps.cap == kMaxUserGates && opreg::kLvl2UserOps.cap == kMaxUserGates2,
+              "the header's capacities are the device tables'");
+static_assert(opreg::kOutputShift == kMaxOutputShift && opreg::kRingN == kN, "the registry's output shift and ring are the kernels'");
+int refuse(opreg::Refusal r) { return r == opreg::Refusal::None ? 0 : fail(-1, opreg::refusal_text(r)); }
 // packed ROM words: op ids that carry an index / an exponent (include/cufhe_amd.h)
-static_assert(CUFHE_AMD_TL_SEIKS_AT(0) > CUFHE_AMD_USER_OP_OUTPUT(CUFHE_AMD_USER_OP_BASE + kMaxUserGates - 1, (1 << kMaxOutputShift) - 1) &&
-                  CUFHE_AMD_TL_SEIKS_AT(0) > CUFHE_AMD_TL_CIRCUIT_BOOTSTRAP && CUFHE_AMD_TL_SEIKS_AT(0) >= CUFHE_AMD_NUM_OPS,
-              "SEIKS_AT ids lie above the built-in, TRLWE-level and user ops");
-static_assert(CUFHE_AMD_TL_CMUX_ROTATE(0) > CUFHE_AMD_TL_SEIKS_AT(kN - 1), "CMUX_ROTATE ids lie above the SEIKS_AT ids");
 bool is_seiks_at(int op) { return op >= CUFHE_AMD_TL_SEIKS_AT(0) && op <= CUFHE_AMD_TL_SEIKS_AT(kN - 1); }
 bool is_cmux_rotate(int op) { return op >= CUFHE_AMD_TL_CMUX_ROTATE(0) && op <= CUFHE_AMD_TL_CMUX_ROTATE(2 * kN - 1); }
 int fail_packed_rom_set() { return fail(-1, "packed ROM words (TRLWE rotation, rotating CMUX, indexed SampleExtract) run on the default path only: not with \"param_set\" active"); }
-
-// User gates of the N = 2048 ring (cufhe_amd_lvl2_define_gate, _define_gate_multi, lvl2.inc.h): definitions of their own in an id range
-// of their own, 64-bit test vectors in row k of every device's DeviceState::tvs2.  Same write-once discipline as g_user; output j of a
-// multi-output definition k is CUFHE_AMD_LVL2_USER_OP_OUTPUT(base + k, j) = base + k + j * CUFHE_AMD_LVL2_MAX_USER_GATES.
-static_assert(CUFHE_AMD_LVL2_MAX_USER_GATES == kMaxUserGates2, "the header's capacity is the device table's");
-static_assert(CUFHE_AMD_LVL2_USER_OP_BASE > CUFHE_AMD_TL_CMUX_ROTATE(2 * kN - 1) && CUFHE_AMD_LVL2_USER_OP_BASE > CUFHE_AMD_TL_SEIKS_AT(kN - 1) &&
-                  CUFHE_AMD_LVL2_USER_OP_BASE >= CUFHE_AMD_USER_OP_BASE + (kMaxUserGates << kMaxOutputShift) &&
-                  CUFHE_AMD_LVL2_USER_OP_BASE > CUFHE_AMD_TL_CIRCUIT_BOOTSTRAP && CUFHE_AMD_LVL2_USER_OP_BASE >= CUFHE_AMD_NUM_OPS,
-              "lvl2 user op ids lie above every other id range");
-static_assert(CUFHE_AMD_LVL2_USER_OP_OUTPUT(CUFHE_AMD_LVL2_USER_OP_BASE + kMaxUserGates2 - 1, (1 << kMaxOutputShift) - 1) ==
-                  CUFHE_AMD_LVL2_USER_OP_BASE + (kMaxUserGates2 << kMaxOutputShift) - 1, "lvl2 output ids fill [base, base + 8 * 64)");
-UserGate g_user2[kMaxUserGates2];
-std::atomic<int> g_user2_count{0};
-bool is_lvl2_user_op(int op) { return op >= CUFHE_AMD_LVL2_USER_OP_BASE && op < CUFHE_AMD_LVL2_USER_OP_BASE + (kMaxUserGates2 << kMaxOutputShift); }
-int lvl2_user_def(int op) { return (op - CUFHE_AMD_LVL2_USER_OP_BASE) % kMaxUserGates2; }      // definition index k of a lvl2 user op id
-int lvl2_user_output(int op) { return (op - CUFHE_AMD_LVL2_USER_OP_BASE) / kMaxUserGates2; }   // output j of a lvl2 user op id
-// the definition of `op`; nullptr when op is not a defined lvl2 user gate or names an output j >= nout of one
-const UserGate* lvl2_user_gate(int op)
-{
-    if (!is_lvl2_user_op(op)) return nullptr;
-    const int k = lvl2_user_def(op);
-    if (k >= g_user2_count.load(std::memory_order_acquire)) return nullptr;
-    return lvl2_user_output(op) < g_user2[k].nout ? &g_user2[k] : nullptr;
-}
-// the refusal of a lvl2 user op id that names no defined gate: the messages of fail_user_op
-int fail_lvl2_user_op(int op)
-{
-    if (lvl2_user_output(op) == 0) return fail(-1, "lvl2 user gate op not defined (cufhe_amd_lvl2_define_gate; CleanUp drops the definitions)");
-    return fail(-1, "unknown gate op: not an output of a defined multi-output user gate (CUFHE_AMD_LVL2_USER_OP_OUTPUT(op, j), j < nout)");
-}
-int fail_lvl2_user_path()
-{
-    return fail(-1, "lvl2 user gates run on the N = 2048 ring only: lvl0 ciphertexts through cufhe_amd_lvl2_gate_batch or with \"lvl0_ring\" 2048, "
-                    "not with \"param_set\" active");
-}
-
-// User gates of the compiled parameter sets (cufhe_amd_ps_define_gate, _define_gate_multi, paramsets.inc.h): one table of definitions
-// for all sets, in an id range of its own, each definition made for ONE set (g_ps_user_set[k]); its test vector (N words of that set) is
-// row k of that set's PsState::tvs on every device.  Same write-once discipline as g_user; output j of a multi-output definition k is
-// CUFHE_AMD_PS_USER_OP_OUTPUT(base + k, j) = base + k + j * CUFHE_AMD_PS_MAX_USER_GATES.  The ids of cufhe_amd_define_gate and
-// cufhe_amd_lvl2_define_gate keep their meaning: they stay refused on a set.
-static_assert(CUFHE_AMD_PS_MAX_USER_GATES == kMaxUserGates, "the header's capacity is the device tables'");
-static_assert(CUFHE_AMD_PS_USER_OP_BASE > CUFHE_AMD_TL_CMUX_ROTATE(2 * kN - 1) &&
-                  CUFHE_AMD_PS_USER_OP_BASE >= CUFHE_AMD_LVL2_USER_OP_BASE + (kMaxUserGates2 << kMaxOutputShift) &&
-                  CUFHE_AMD_PS_USER_OP_BASE >= CUFHE_AMD_USER_OP_BASE + (kMaxUserGates << kMaxOutputShift) &&
-                  CUFHE_AMD_PS_USER_OP_BASE > CUFHE_AMD_TL_SEIKS_AT(kN - 1) && CUFHE_AMD_PS_USER_OP_BASE > CUFHE_AMD_TL_CIRCUIT_BOOTSTRAP,
-              "parameter-set user op ids lie above every other id range");
-static_assert(CUFHE_AMD_PS_USER_OP_OUTPUT(CUFHE_AMD_PS_USER_OP_BASE + kMaxUserGates - 1, (1 << kMaxOutputShift) - 1) ==
-                  CUFHE_AMD_PS_USER_OP_BASE + (kMaxUserGates << kMaxOutputShift) - 1, "parameter-set output ids fill [base, base + 8 * 64)");
-UserGate g_ps_user[kMaxUserGates];
-int g_ps_user_set[kMaxUserGates];
-std::atomic<int> g_ps_user_count{0};
-bool is_ps_user_op(int op) { return op >= CUFHE_AMD_PS_USER_OP_BASE && op < CUFHE_AMD_PS_USER_OP_BASE + (kMaxUserGates << kMaxOutputShift); }
-int ps_user_def(int op) { return (op - CUFHE_AMD_PS_USER_OP_BASE) % kMaxUserGates; }      // definition index k of a set's user op id
-int ps_user_output(int op) { return (op - CUFHE_AMD_PS_USER_OP_BASE) / kMaxUserGates; }   // output j of a set's user op id
-// the definition of `op` made for parameter set `set`; nullptr when op is not a defined user gate of that set or names an output
-// j >= nout of one
-const UserGate* ps_user_gate(int op, int set)
-{
-    if (!is_ps_user_op(op) || set < 0) return nullptr;
-    const int k = ps_user_def(op);
-    if (k >= g_ps_user_count.load(std::memory_order_acquire) || g_ps_user_set[k] != set) return nullptr;
-    return ps_user_output(op) < g_ps_user[k].nout ? &g_ps_user[k] : nullptr;
-}
-// the refusal of an id of the range that is no defined user gate of parameter set `set`
-int fail_ps_user_op(int op, int set)
-{
-    const int k = ps_user_def(op);
-    if (k >= g_ps_user_count.load(std::memory_order_acquire))
-        return fail(-1, "parameter set user gate op not defined (cufhe_amd_ps_define_gate; CleanUp drops the definitions)");
-    if (g_ps_user_set[k] != set) return fail(-1, "user gate op was defined for another parameter set (cufhe_amd_ps_define_gate(set, ...))");
-    return fail(-1, "unknown gate op: not an output of a defined multi-output user gate of this parameter set (CUFHE_AMD_PS_USER_OP_OUTPUT(op, j), j < nout)");
-}
-int fail_ps_user_path()
-{
-    return fail(-1, "user gates of a parameter set run on that set only: through cufhe_amd_ps_gate_batch or with \"param_set\" active, "
-                    "not on the default path or on the N = 2048 ring");
-}
-
-int user_def(int op) { return (op - CUFHE_AMD_USER_OP_BASE) % kMaxUserGates; }      // definition index k of a user op id
-int user_output(int op) { return (op - CUFHE_AMD_USER_OP_BASE) / kMaxUserGates; }   // output j of a user op id
-// the definition of `op`; nullptr when op is not a defined user gate or names an output j >= nout of one
-const UserGate* user_gate(int op)
-{
-    if (!is_user_op(op)) return nullptr;
-    const int k = user_def(op);
-    if (k >= g_user_count.load(std::memory_order_acquire)) return nullptr;
-    return user_output(op) < g_user[k].nout ? &g_user[k] : nullptr;
-}
-// the refusal of a user op id that names no defined gate: an undefined definition, or an output id (j > 0) that no multi-output
-// definition has
-int fail_user_op(int op)
-{
-    if (user_output(op) == 0) return fail(-1, "user gate op not defined (cufhe_amd_define_gate; CleanUp drops the definitions)");
-    return fail(-1, "unknown gate op: not an output of a defined multi-output user gate (CUFHE_AMD_USER_OP_OUTPUT(op, j), j < nout)");
-}
-// operands a user gate reads: in0 (c1 = c2 = 0), in0 and in1 (c2 = 0), all three
-int user_gate_arity(const UserGate& u) { return u.c[2] ? 3 : u.c[1] ? 2 : 1; }
 
 template <class GetGate>
 int run_gates_lvl2(int device, void* stream, size_t count, GetGate get);   // lvl2.inc.h
@@ -649,42 +544,20 @@ long g_param_set = -1;
 //   ks_mu              the mu of the Mux sum in the key switch
 //   lvl1_gates         whether it has gates on Mid ciphertexts (level 1)
 //   s, ready(), rotate(), keyswitch()   its device, the readiness check and the two launchers
-//   user_gates         whether its rotation kernels read LinDesc::pad as a test-vector row (user gates: the default path with the ids of
-//                      cufhe_amd_define_gate, a parameter set with those of cufhe_amd_ps_define_gate made for it)
-//   set_index          the compiled parameter set the path runs on, -1 for the default path and the N = 2048 ring
-//   lvl2_user_gates    whether it runs the lvl2 user gates (RotDesc2::pad = make_pad2(row, s); the N = 2048 ring only); then rotate() takes
-//                      one more argument: whether any descriptor names a row (so does a parameter set's: set_index >= 0)
-//   user_op(op), tv_pad(op, u)   the path's own definition lookup (nullptr: not a defined user gate of this path) and pad rule
-//   user_def(op), user_output(op), multi_pad(op, u)   definition index and output j of a user op id of the path, and the pad of a
-//                      multi-output definition's rotation (row and output shift)
+//   path, set_index    the route it is (opreg::Path) and the compiled parameter set it runs on, -1 for the default path and the N = 2048
+//                      ring: which user gates it runs is the registry's rule (op_registry.h)
+//   pad(row, s)        the rotation descriptor's pad that names row `row` of its test-vector table with 2^s outputs
+//   rotate_takes_tv_rows   whether rotate() takes one more argument: whether any descriptor names a row
 // Level 0: blind rotate -> key switch (__HomGate__ br -> iks); level 1: key switch -> blind rotate (iks -> br); Not / Copy and the
 // level-1 Mux sums run last, as one lincomb.  The three-input user gates' c0 in0 + c1 in1 run first, as one lincomb into temporaries.
 template <class P, class GetGate>
 int lower_gates(const P& p, hipStream_t st, int level, size_t count, GetGate get)
 {
     using Mid = typename P::Mid;
-    if constexpr (!P::user_gates || P::set_index >= 0) {
-        for (size_t g = 0; g < count; g++)
-            if (is_user_op(get(g).op))
-                return fail(-1, "user gates run on the default path only: not with \"param_set\" active or on the N = 2048 ring (\"lvl0_ring\")");
-    }
-    for (size_t g = 0; g < count; g++) {      // a set's user gates: on that set only
-        const int op = get(g).op;
-        if (!is_ps_user_op(op)) continue;
-        if (P::set_index < 0) return fail_ps_user_path();
-        if (!ps_user_gate(op, P::set_index)) return fail_ps_user_op(op, P::set_index);
-    }
-    if constexpr (!P::lvl2_user_gates) {
-        for (size_t g = 0; g < count; g++)
-            if (is_lvl2_user_op(get(g).op)) return fail_lvl2_user_path();
-    } else {
-        for (size_t g = 0; g < count; g++) {
-            const int op = get(g).op;
-            if (!is_lvl2_user_op(op)) continue;
-            if (g_param_set >= 0 || level != 0) return fail_lvl2_user_path();
-            if (!lvl2_user_gate(op)) return fail_lvl2_user_op(op);
-        }
-    }
+    // every id is put to the registry once; what it answers (the definition, its row and the output) serves both passes below
+    std::vector<opreg::Admission> adm;        // stays empty for a list without a user gate's id
+    const opreg::Route route{P::path, P::set_index, level, g_param_set >= 0};
+    if (int rc = refuse(opreg::admit_list(g_ops, count, [&](size_t g) { return get(g).op; }, route, opreg::Entry::Direct, &adm))) return rc;
     if (int rc = p.ready()) return rc;
     if (level != 0 && level != 1) return fail(-1, "level must be 0 or 1");
     if (count == 0) return 0;
@@ -702,29 +575,24 @@ int lower_gates(const P& p, hipStream_t st, int level, size_t count, GetGate get
     size_t nrot = 0, npre = 0;
     for (size_t g = 0; g < count; g++) {
         const int op = get(g).op;
-        if constexpr (P::user_gates || P::lvl2_user_gates) {
-            const UserGate* u = P::user_op(op);
-            if (P::user_gates && P::set_index < 0 && is_user_op(op) && !u) return fail_user_op(op);
-            if (u) {
-                if (u->nout > 1) {
-                    const GateRef gr = get(g);
-                    const int arity = user_gate_arity(*u);
-                    const auto key = std::make_tuple(P::user_def(op), (const uint32_t*)gr.in0, arity >= 2 ? gr.in1 : nullptr, arity == 3 ? gr.in2 : nullptr);
-                    if (fuse.empty()) fuse.assign(count, (size_t)-1);
-                    auto it = evals.find(key);
-                    if (it == evals.end()) {
-                        it = evals.emplace(key, ev.size()).first;
-                        ev.push_back({nullptr, nullptr, false});
-                        nmulti_words += (size_t)u->nout;
-                        if (arity == 3) npre += 1;
-                    }
-                    fuse[g] = it->second;
-                    continue;
+        if (const UserGate* u = adm.empty() ? nullptr : adm[g].gate) {
+            const int arity = user_gate_arity(*u);
+            bool rotation = true;        // the gate brings a rotation of its own: not the second, third, .. output of an evaluation
+            if (u->nout > 1) {
+                const GateRef gr = get(g);
+                const auto key = std::make_tuple(adm[g].k, (const uint32_t*)gr.in0, arity >= 2 ? gr.in1 : nullptr, arity == 3 ? gr.in2 : nullptr);
+                if (fuse.empty()) fuse.assign(count, (size_t)-1);
+                const auto [it, fresh] = evals.emplace(key, ev.size());
+                if ((rotation = fresh)) {
+                    ev.push_back({nullptr, nullptr, false});
+                    nmulti_words += (size_t)u->nout;
                 }
+                fuse[g] = it->second;
+            } else {
                 nrot += 1;
-                if (user_gate_arity(*u) == 3) npre += 1;
-                continue;
             }
+            if (rotation && arity == 3) npre += 1;
+            continue;
         }
         if (op < 0 || op >= CUFHE_AMD_NUM_OPS) return fail(-1, "unknown gate op");
         if (op == CUFHE_AMD_MUX || op == CUFHE_AMD_NMUX) nrot += 2;
@@ -763,71 +631,40 @@ int lower_gates(const P& p, hipStream_t st, int level, size_t count, GetGate get
     for (size_t g = 0; g < count; g++) {
         const GateRef gr = get(g);
         if (!gr.out || !gr.in0) return fail(-1, "null ciphertext pointer");
-        if constexpr (P::user_gates || P::lvl2_user_gates) {
-            if (const UserGate* u = P::user_op(gr.op); u && u->nout > 1) {
-                // output j of a multi-output evaluation: the evaluation's one rotation is emitted with its first requested output;
-                // level 0: the key switch of scratch output j into out; level 1: a copy of scratch output j into out (last lincomb)
-                const int arity = user_gate_arity(*u);
-                if (arity >= 2 && !gr.in1) return fail(-1, "user gate needs a second operand");
-                if (arity == 3 && !gr.in2) return fail(-1, "user gate needs a third operand");
-                Eval& e = ev[fuse[g]];
-                if (!e.done) {
-                    e.done = true;
+        if (const UserGate* u = adm.empty() ? nullptr : adm[g].gate) {
+            // x = c0 in0 + c1 in1 + c2 in2 + (0, ..., 0, off) through the two-input gate path; the rotation starts from the definition's
+            // test vector (pad: its row and output shift) or from mu (pad 0).  Output j of a multi-output evaluation: the evaluation's
+            // one rotation is emitted with its first requested output and writes all nout outputs to scratch
+            if (const char* missing = opreg::missing_operand(*u, gr.in1 != nullptr, gr.in2 != nullptr)) return fail(-1, missing);
+            const uint32_t pad = u->tv ? P::pad(adm[g].k, u->s) : 0u;
+            tv_rows |= pad != 0;
+            const bool multi = u->nout > 1;
+            Eval own{nullptr, nullptr, false};
+            Eval& e = multi ? ev[fuse[g]] : own;
+            if (!e.done) {
+                e.done = true;
+                if (multi) {
                     e.t1 = (uint32_t*)(tmpm + im * P::mid_words);
+                    e.t0 = level ? tmpm0 + fuse[g] * P::lvl0_words : nullptr;
                     im += (size_t)u->nout;
-                    const uint32_t* a = gr.in0;
-                    const uint32_t* b = arity >= 2 ? gr.in1 : gr.in0;
-                    int32_t ca = u->c[0], cb = u->c[1];
-                    if (arity == 3) {
-                        uint32_t* t = tmpp + pre.size() * level_words;
-                        pre.push_back({gr.in0, gr.in1, t, u->c[0], u->c[1], 0u, 0u});
-                        a = t; b = gr.in2; ca = 1; cb = u->c[2];
-                    }
-                    const uint32_t pad = P::multi_pad(gr.op, *u);
-                    tv_rows = true;
-                    if (level == 0) {
-                        rot.push_back({a, b, (Mid*)e.t1, ca, cb, u->off, pad});
-                    } else if constexpr (P::lvl1_gates) {
-                        e.t0 = tmpm0 + fuse[g] * P::lvl0_words;
-                        ks.push_back({a, b, e.t0, ca, cb, u->off});
-                        rot.push_back({e.t0, e.t0, (Mid*)e.t1, 1, 0, 0u, pad});
-                    }
+                } else {      // level 1: the rotation writes straight to `out`
+                    e.t1 = level ? gr.out : (uint32_t*)(tmp1 + ir * P::mid_words);
+                    e.t0 = level ? tmp0 + ir * P::lvl0_words : nullptr;
+                    ir += 1;
                 }
-                Mid* tj = (Mid*)e.t1 + (size_t)P::user_output(gr.op) * P::mid_words;
-                if (level == 0) ks.push_back({tj, tj, gr.out, 1, 0, 0u});
-                else lin.push_back({(const uint32_t*)tj, (const uint32_t*)tj, (uint32_t*)gr.out, 1, 0, 0u, 0u});
-                continue;
-            }
-        }
-        if constexpr (P::user_gates || P::lvl2_user_gates) {
-            if (const UserGate* u = P::user_op(gr.op)) {
-                // x = c0 in0 + c1 in1 + c2 in2 + (0, ..., 0, off) through the two-input gate path; the rotation starts from the
-                // definition's test vector (LinDesc::pad = row + 1) or from mu (pad 0)
-                const int arity = user_gate_arity(*u);
-                if (arity >= 2 && !gr.in1) return fail(-1, "user gate needs a second operand");
-                if (arity == 3 && !gr.in2) return fail(-1, "user gate needs a third operand");
-                const uint32_t* a = gr.in0;
-                const uint32_t* b = arity >= 2 ? gr.in1 : gr.in0;
-                int32_t ca = u->c[0], cb = u->c[1];
-                if (arity == 3) {
-                    uint32_t* t = tmpp + pre.size() * level_words;
-                    pre.push_back({gr.in0, gr.in1, t, u->c[0], u->c[1], 0u, 0u});
-                    a = t; b = gr.in2; ca = 1; cb = u->c[2];
-                }
-                const uint32_t pad = P::tv_pad(gr.op, *u);
-                tv_rows |= pad != 0;
+                const opreg::GateOperands x = opreg::user_gate_operands(*u, gr.in0, gr.in1, gr.in2, [&] { return tmpp + pre.size() * level_words; }, pre);
                 if (level == 0) {
-                    Mid* t1 = tmp1 + ir * P::mid_words;
-                    rot.push_back({a, b, t1, ca, cb, u->off, pad});
-                    ks.push_back({t1, t1, gr.out, 1, 0, 0u});
+                    rot.push_back({x.a, x.b, (Mid*)e.t1, x.ca, x.cb, u->off, pad});
                 } else if constexpr (P::lvl1_gates) {
-                    uint32_t* t0 = tmp0 + ir * P::lvl0_words;
-                    ks.push_back({a, b, t0, ca, cb, u->off});
-                    rot.push_back({t0, t0, gr.out, 1, 0, 0u, pad});
+                    ks.push_back({x.a, x.b, e.t0, x.ca, x.cb, u->off});
+                    rot.push_back({e.t0, e.t0, (Mid*)e.t1, 1, 0, 0u, pad});
                 }
-                ir += 1;
-                continue;
             }
+            // level 0: the key switch of output j into out; level 1: a copy of scratch output j into out (last lincomb)
+            Mid* tj = (Mid*)e.t1 + (size_t)adm[g].j * P::mid_words;
+            if (level == 0) ks.push_back({tj, tj, gr.out, 1, 0, 0u});
+            else if (multi) lin.push_back({(const uint32_t*)tj, (const uint32_t*)tj, (uint32_t*)gr.out, 1, 0, 0u, 0u});
+            continue;
         }
         if (gr.op == CUFHE_AMD_NOT || gr.op == CUFHE_AMD_COPY) {
             lin.push_back({gr.in0, gr.in0, gr.out, gr.op == CUFHE_AMD_NOT ? -1 : 1, 0, 0u, 0u});
@@ -878,20 +715,16 @@ int lower_gates(const P& p, hipStream_t st, int level, size_t count, GetGate get
     if (int rc = upload_descs(p.s, sc, lin, &dlin)) return rc;
     if (int rc = upload_descs(p.s, sc, pre, &dpre)) return rc;
     if (int rc = launch_lincomb(st, dpre, pre.size(), (int)level_words)) return rc;
+    auto rotate = [&] {
+        if constexpr (P::rotate_takes_tv_rows) return p.rotate(st, drot, rot.size(), P::n, nullptr, tv_rows);
+        else return p.rotate(st, drot, rot.size(), P::n, nullptr);
+    };
     if (level == 0) {
-        if constexpr (P::lvl2_user_gates || P::set_index >= 0) {
-            if (int rc = p.rotate(st, drot, rot.size(), P::n, nullptr, tv_rows)) return rc;
-        } else {
-            if (int rc = p.rotate(st, drot, rot.size(), P::n, nullptr)) return rc;
-        }
+        if (int rc = rotate()) return rc;
         if (int rc = p.keyswitch(st, dks, ks.size())) return rc;
     } else if constexpr (P::lvl1_gates) {
         if (int rc = p.keyswitch(st, dks, ks.size())) return rc;
-        if constexpr (P::set_index >= 0) {
-            if (int rc = p.rotate(st, drot, rot.size(), P::n, nullptr, tv_rows)) return rc;
-        } else {
-            if (int rc = p.rotate(st, drot, rot.size(), P::n, nullptr)) return rc;
-        }
+        if (int rc = rotate()) return rc;
     }
     return launch_lincomb(st, dlin, lin.size(), level ? P::mid_words : P::lvl0_words);
 }
@@ -1033,13 +866,10 @@ struct BasePath {
     using Mid = uint32_t;
     static constexpr int lvl0_words = kLvl0Words, mid_words = kLvl1Words, n = kLvl0N;
     static constexpr uint32_t ks_mu = kMu;
-    static constexpr bool lvl1_gates = true, has_cmux = true, user_gates = true, packed_rom = true, lvl2_user_gates = false;
+    static constexpr bool lvl1_gates = true, has_cmux = true, packed_rom = true, rotate_takes_tv_rows = false;
+    static constexpr opreg::Path path = opreg::Path::Default;
     static constexpr int set_index = -1;
-    static const UserGate* user_op(int op) { return user_gate(op); }
-    static int user_def(int op) { return ::user_def(op); }
-    static int user_output(int op) { return ::user_output(op); }
-    static uint32_t multi_pad(int op, const UserGate& u) { return make_pad(::user_def(op), u.s); }
-    static uint32_t tv_pad(int op, const UserGate& u) { return u.tv ? (uint32_t)(op - CUFHE_AMD_USER_OP_BASE) + 1 : 0u; }
+    static constexpr uint32_t pad(int row, int s) { return make_pad(row, s); }
     static constexpr size_t trlwe_words = 2 * kN;
     static constexpr auto se_kernel = sample_extract_desc_kernel;
     DeviceState& s;
@@ -1058,32 +888,15 @@ struct BasePath {
     int cmux(hipStream_t st, const CmuxDesc* d, size_t count) const { return launch_cmux(cmux_desc_kernel, st, d, count); }
     int cmux_rotate(hipStream_t st, const CmuxRotDesc* d, size_t count) const { return launch_cmux(cmux_rotate_desc_kernel, st, d, count); }
 };
+static_assert([] { for (int k = 0; k < kMaxUserGates; k++) if (BasePath::pad(k, 0) != (uint32_t)(opreg::kUserOps.id(k) - CUFHE_AMD_USER_OP_BASE) + 1) return false; return true; }(),
+              "a single-output definition's pad is LinDesc::pad's row + 1: (op - CUFHE_AMD_USER_OP_BASE) + 1 for its one id");
 
 template <class GetGate>
 int run_gates(int device, void* stream, int level, size_t count, GetGate get)
 {
-    // user ops are refused before any device work when they are not defined or the path they would take has no test-vector table
-    const bool user_ok = g_param_set < 0 && !(level == 0 && g_lvl0_ring == 2048);
-    for (size_t g = 0; g < count; g++) {
-        const int op = get(g).op;
-        if (!is_user_op(op)) continue;
-        if (!user_gate(op)) return fail_user_op(op);
-        if (!user_ok) return fail(-1, "user gates run on the default path only: not with \"param_set\" active or on the N = 2048 ring (\"lvl0_ring\")");
-    }
-    // lvl2 user ops: only where the gates run through the N = 2048 ring
-    for (size_t g = 0; g < count; g++) {
-        const int op = get(g).op;
-        if (!is_lvl2_user_op(op)) continue;
-        if (g_param_set >= 0 || level != 0 || g_lvl0_ring != 2048) return fail_lvl2_user_path();
-        if (!lvl2_user_gate(op)) return fail_lvl2_user_op(op);
-    }
-    // a parameter set's user ops: only while the gates run on the set they were defined for
-    for (size_t g = 0; g < count; g++) {
-        const int op = get(g).op;
-        if (!is_ps_user_op(op)) continue;
-        if (g_param_set < 0 || (level == 0 && g_lvl0_ring == 2048)) return fail_ps_user_path();
-        if (!ps_user_gate(op, (int)g_param_set)) return fail_ps_user_op(op, (int)g_param_set);
-    }
+    // user ops are refused before any device work when they are not defined or the path they would take does not run them
+    const opreg::Route route = opreg::route_of_options(g_param_set, g_lvl0_ring, level);
+    if (int rc = refuse(opreg::admit_list(g_ops, count, [&](size_t g) { return get(g).op; }, route, opreg::Entry::List, nullptr))) return rc;
     if (level == 0 && g_lvl0_ring == 2048) return run_gates_lvl2(device, stream, count, get);
     if ((level == 0 || level == 1) && g_param_set >= 0) return run_gates_ps((int)g_param_set, device, stream, level, count, get);
     if (int rc = use_device(device)) return rc;
@@ -1167,6 +980,48 @@ void build_ksk_matrix(const uint32_t* ksk_padded, ksmm_v4i** out)
     *out = p;
 }
 
+
+// A new definition of `table` (the caller holds g_mu): every device must be ready(i), else -3 with `not_ready`; the table must have
+// room, else `full`.  If it `writes`, write_row(i, k) then puts the definition's test vector into row k of device i's table (device i is
+// current), synchronously like the key replicas: no launch reads the row before its id exists; else no device is touched.
+template <class Table, class Def, class Ready, class WriteRow>
+int define_op(Table& table, const Def& def, Ready ready, const char* not_ready, const char* full, bool writes, WriteRow write_row, int* op)
+{
+    for (int i = 0; i < g_gpu_num; i++)
+        if (!ready(i)) return fail(-3, not_ready);
+    const int k = table.next_free();
+    if (k < 0) return fail(-1, full);
+    for (int i = 0; writes && i < g_gpu_num; i++) {
+        HIP_TRY(hipSetDevice(phys_device(i)));
+        if (int rc = write_row(i, k)) return rc;
+    }
+    *op = table.publish(k, def);
+    return 0;
+}
+// row k of a table of `rows` rows of `words` words that is allocated when its first row is written
+template <class T>
+int write_tv_row(T** table, int rows, size_t words, int k, const T* test_vector)
+{
+    if (!*table) {
+        DevPtr<T> t;
+        HIP_TRY(t.alloc((size_t)rows * words));
+        *table = t.release();
+    }
+    HIP_TRY(hipMemcpy(*table + (size_t)k * words, test_vector, words * sizeof(T), hipMemcpyHostToDevice));
+    return 0;
+}
+UserGate make_user_gate(const int32_t coeffs[3], uint32_t offset, bool tv, int s) { return UserGate{{coeffs[0], coeffs[1], coeffs[2]}, offset, tv, 1 << s, s}; }
+
+// a user gate of the default path with nout = 2^s outputs (1: cufhe_amd_define_gate); the caller holds g_mu
+int define_user_gate(const int32_t coeffs[3], uint32_t offset, const uint32_t* test_vector, int s, int* op)
+{
+    if (!coeffs || !op) return fail(-1, "null pointer");
+    if (coeffs[0] == 0) return fail(-1, "user gate: c0 must not be 0");
+    if (g_param_set >= 0) return fail(-1, "user gates run on the default path only: not while \"param_set\" is active");
+    return define_op(g_ops.user, make_user_gate(coeffs, offset, test_vector != nullptr, s), [](int i) { return g_dev[i].keys_ready; },
+                     "Initialize(ek) has not been called for every device", "user gate table full (CUFHE_AMD_MAX_USER_GATES definitions until CleanUp)",
+                     test_vector != nullptr, [&](int i, int k) { return write_tv_row(&g_dev[i].tvs, kMaxUserGates, kN, k, test_vector); }, op);
+}
 }  // namespace
 
 #include "sched_hip.inc.h"
@@ -1352,9 +1207,7 @@ int cufhe_amd_cleanup(void)
         s.prof = cufhe_amd_profile{};
     }
     lvl2_release_host_key();
-    g_user_count.store(0, std::memory_order_release);
-    g_user2_count.store(0, std::memory_order_release);
-    g_ps_user_count.store(0, std::memory_order_release);
+    g_ops.user.clear(); g_ops.lvl2.clear(); g_ops.ps.clear();
     return 0;
 }
 
@@ -1495,35 +1348,6 @@ int cufhe_amd_gate_list(int device, void* stream, int level, size_t count, const
     return run_gates(device, stream, level, count, [&](size_t g) {
         return GateRef{ops[g], outs[g], in0s[g], in1s ? in1s[g] : nullptr, in2s ? in2s[g] : nullptr};
     });
-}
-
-// definition k = g_user_count of a user gate with nout = 2^s outputs (1: cufhe_amd_define_gate); the caller holds g_mu
-int define_user_gate(const int32_t coeffs[3], uint32_t offset, const uint32_t* test_vector, int s, int* op)
-{
-    if (!coeffs || !op) return fail(-1, "null pointer");
-    if (coeffs[0] == 0) return fail(-1, "user gate: c0 must not be 0");
-    if (g_param_set >= 0) return fail(-1, "user gates run on the default path only: not while \"param_set\" is active");
-    for (int i = 0; i < g_gpu_num; i++)
-        if (!g_dev[i].keys_ready) return fail(-3, "Initialize(ek) has not been called for every device");
-    const int k = g_user_count.load(std::memory_order_relaxed);
-    if (k >= kMaxUserGates) return fail(-1, "user gate table full (CUFHE_AMD_MAX_USER_GATES definitions until CleanUp)");
-    if (test_vector) {
-        // row k of every device's table, synchronously (like the key replicas); no launch reads the row before its id exists
-        for (int i = 0; i < g_gpu_num; i++) {
-            DeviceState& s = g_dev[i];
-            HIP_TRY(hipSetDevice(phys_device(i)));
-            if (!s.tvs) {
-                DevPtr<uint32_t> t;
-                HIP_TRY(t.alloc((size_t)kMaxUserGates * kN));
-                s.tvs = t.release();
-            }
-            HIP_TRY(hipMemcpy(s.tvs + (size_t)k * kN, test_vector, kN * sizeof(uint32_t), hipMemcpyHostToDevice));
-        }
-    }
-    g_user[k] = UserGate{{coeffs[0], coeffs[1], coeffs[2]}, offset, test_vector != nullptr, 1 << s, s};
-    g_user_count.store(k + 1, std::memory_order_release);
-    *op = CUFHE_AMD_USER_OP_BASE + k;
-    return 0;
 }
 
 int cufhe_amd_define_gate(const int32_t coeffs[3], uint32_t offset, const uint32_t* test_vector, int* op)

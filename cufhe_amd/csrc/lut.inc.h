@@ -55,53 +55,11 @@ int upload_lut_rotations(DeviceState& s, Scratch& sc, size_t count, const uint32
 
 
 // ---- the recorded forms ----
-// Op-id ranges of the recorded forms against every other range (the ids and their bounds: include/cufhe_amd.h)
-constexpr int kLookupOpEnd = CUFHE_AMD_LOOKUP_OP_OUTPUT(CUFHE_AMD_LOOKUP_OP_BASE + CUFHE_AMD_MAX_LOOKUPS - 1, (1 << kMaxOutputShift) - 1) + 1;
-constexpr int kSpreadOpEnd = CUFHE_AMD_TL_SPREAD(10, 0) + 1;          // a + b <= 10: the largest id is (10, 0)
-constexpr int kLutRotateOpEnd = CUFHE_AMD_TL_LUT_ROTATE(kMaxOutputShift) + 1;
-constexpr bool id_ranges_apart(int a0, int a1, int b0, int b1) { return a1 <= b0 || b1 <= a0; }      // [a0, a1) and [b0, b1)
-constexpr bool apart_from_existing(int lo, int hi)
-{
-    return id_ranges_apart(lo, hi, 0, CUFHE_AMD_NUM_OPS) && id_ranges_apart(lo, hi, CUFHE_AMD_TL_BOOTSTRAP, CUFHE_AMD_TL_CIRCUIT_BOOTSTRAP + 1) &&
-           id_ranges_apart(lo, hi, CUFHE_AMD_USER_OP_BASE, CUFHE_AMD_USER_OP_BASE + (kMaxUserGates << kMaxOutputShift) + 1) &&
-           id_ranges_apart(lo, hi, CUFHE_AMD_TL_SEIKS_AT(0), CUFHE_AMD_TL_SEIKS_AT(kN - 1) + 1) &&
-           id_ranges_apart(lo, hi, CUFHE_AMD_TL_CMUX_ROTATE(0), CUFHE_AMD_TL_CMUX_ROTATE(2 * kN - 1) + 1) &&
-           id_ranges_apart(lo, hi, CUFHE_AMD_LVL2_USER_OP_BASE, CUFHE_AMD_LVL2_USER_OP_BASE + (kMaxUserGates2 << kMaxOutputShift)) &&
-           id_ranges_apart(lo, hi, CUFHE_AMD_PS_USER_OP_BASE, CUFHE_AMD_PS_USER_OP_BASE + (kMaxUserGates << kMaxOutputShift));
-}
-static_assert(CUFHE_AMD_MAX_LOOKUPS == kMaxLookups && kLookupOpEnd == CUFHE_AMD_LOOKUP_OP_BASE + (kMaxLookups << kMaxOutputShift),
-              "lookup output ids fill [base, base + 8 * 64)");
-static_assert(apart_from_existing(CUFHE_AMD_LOOKUP_OP_BASE, kLookupOpEnd), "lookup ids overlap no other op id");
-static_assert(apart_from_existing(CUFHE_AMD_TL_SPREAD_BASE, kSpreadOpEnd), "recorded Spread ids overlap no other op id");
-static_assert(apart_from_existing(CUFHE_AMD_TL_LUT_ROTATE_BASE, kLutRotateOpEnd), "recorded table-rotation ids overlap no other op id");
-static_assert(id_ranges_apart(CUFHE_AMD_TL_SPREAD_BASE, kSpreadOpEnd, CUFHE_AMD_TL_LUT_ROTATE_BASE, kLutRotateOpEnd) &&
-                  id_ranges_apart(CUFHE_AMD_TL_SPREAD_BASE, kSpreadOpEnd, CUFHE_AMD_LOOKUP_OP_BASE, kLookupOpEnd) &&
-                  id_ranges_apart(CUFHE_AMD_TL_LUT_ROTATE_BASE, kLutRotateOpEnd, CUFHE_AMD_LOOKUP_OP_BASE, kLookupOpEnd),
-              "the three new ranges do not overlap one another");
-static_assert(apart_from_existing(CUFHE_AMD_TL_PACK, CUFHE_AMD_TL_PACK + 1) &&
-                  id_ranges_apart(CUFHE_AMD_TL_PACK, CUFHE_AMD_TL_PACK + 1, CUFHE_AMD_TL_SPREAD_BASE, kSpreadOpEnd) &&
-                  id_ranges_apart(CUFHE_AMD_TL_PACK, CUFHE_AMD_TL_PACK + 1, CUFHE_AMD_TL_LUT_ROTATE_BASE, kLutRotateOpEnd) &&
-                  id_ranges_apart(CUFHE_AMD_TL_PACK, CUFHE_AMD_TL_PACK + 1, CUFHE_AMD_LOOKUP_OP_BASE, kLookupOpEnd),
-              "the recorded pack's id (pack.inc.h) overlaps no other op id");
-
-LookupDef g_lookup[kMaxLookups];
-std::atomic<int> g_lookup_count{0};      // published with release once the entry is written (definitions are immutable)
-
-bool is_lookup_op(int op) { return op >= CUFHE_AMD_LOOKUP_OP_BASE && op < kLookupOpEnd; }
-bool is_spread_op(int op) { return op >= CUFHE_AMD_TL_SPREAD_BASE && op < kSpreadOpEnd; }
-bool is_lut_rotate_op(int op) { return op >= CUFHE_AMD_TL_LUT_ROTATE_BASE && op < kLutRotateOpEnd; }
-bool is_lut_op(int op) { return is_lookup_op(op) || is_spread_op(op) || is_lut_rotate_op(op); }
-int lookup_index(int op) { return (op - CUFHE_AMD_LOOKUP_OP_BASE) % kMaxLookups; }
-int lookup_output(int op) { return (op - CUFHE_AMD_LOOKUP_OP_BASE) / kMaxLookups; }
-// the definition of a lookup OUTPUT id; nullptr: not defined, or an output the definition does not have
-const LookupDef* lookup_def(int op)
-{
-    if (!is_lookup_op(op)) return nullptr;
-    const int k = lookup_index(op);
-    if (k >= g_lookup_count.load(std::memory_order_acquire)) return nullptr;
-    return lookup_output(op) < g_lookup[k].nout ? &g_lookup[k] : nullptr;
-}
-void lut_forget_definitions() { g_lookup_count.store(0, std::memory_order_release); }
+// The ids of the recorded forms, their ranges against every other range, and the lookups' definitions (g_ops.lookup): op_registry.h
+using opreg::kLookupOps;
+bool is_spread_op(int op) { return op >= CUFHE_AMD_TL_SPREAD_BASE && op < opreg::kSpreadOpEnd; }
+bool is_lut_rotate_op(int op) { return op >= CUFHE_AMD_TL_LUT_ROTATE_BASE && op < opreg::kLutRotateOpEnd; }
+bool is_lut_op(int op) { return kLookupOps.contains(op) || is_spread_op(op) || is_lut_rotate_op(op); }
 
 int log2_exact(long long v)      // -1 unless v is a power of two >= 1
 {
@@ -135,13 +93,13 @@ int lower_lut_ops(DeviceState& s, hipStream_t st, const GateRef* g, size_t n)
     for (size_t i = 0; i < n; i++) {
         const GateRef& gr = g[i];
         if (!gr.out || !gr.in0) return fail(-1, "null ciphertext pointer");
-        if (is_lookup_op(gr.op)) {
-            const LookupDef* d = lookup_def(gr.op);
+        if (kLookupOps.contains(gr.op)) {
+            const LookupDef* d = g_ops.lookup.find(gr.op);
             if (!d) return fail(-1, "lookup op " + std::to_string(gr.op) + " is not defined (cufhe_amd_define_lookup)");
             if (!gr.in2) return fail(-1, "lookup without a table");
             if (d->c[1] != 0 && !gr.in1) return fail(-1, "lookup needs a second address operand");
             const uint32_t* in1 = d->c[1] != 0 ? gr.in1 : nullptr;
-            const auto key = std::make_tuple(lookup_index(gr.op), gr.in0, in1, gr.in2);
+            const auto key = std::make_tuple(kLookupOps.def(gr.op), gr.in0, in1, gr.in2);
             auto it = evals.find(key);
             if (it == evals.end()) {
                 it = evals.emplace(key, ev.size()).first;
@@ -179,8 +137,8 @@ int lower_lut_ops(DeviceState& s, hipStream_t st, const GateRef* g, size_t n)
     }
     for (size_t i = 0; i < n; i++) {
         const GateRef& gr = g[i];
-        if (is_lookup_op(gr.op)) {
-            uint32_t* tj = t1 + (ev[fuse[i]].first + (size_t)lookup_output(gr.op)) * kLvl1Words;
+        if (kLookupOps.contains(gr.op)) {
+            uint32_t* tj = t1 + (ev[fuse[i]].first + (size_t)kLookupOps.output(gr.op)) * kLvl1Words;
             ks.push_back({tj, tj, gr.out, 1, 0, 0u, 0u});
         } else if (is_lut_rotate_op(gr.op)) {       // operands (table, addr, -)
             uint32_t* acc = accs + rot2.size() * 2 * kN;
@@ -227,14 +185,10 @@ int cufhe_amd_define_lookup(const int32_t coeffs[2], uint32_t offset, int nout, 
     const int s = log2_exact(nout);
     if (s < 0 || s > kMaxOutputShift) return fail(-1, "define_lookup: nout must be 1, 2, 4 or 8");
     if (g_param_set >= 0) return fail_lut_set();
-    for (int i = 0; i < g_gpu_num; i++)
-        if (!g_dev[i].keys_ready) return fail(-3, "Initialize(ek) has not been called for every device");
-    const int k = g_lookup_count.load(std::memory_order_relaxed);
-    if (k >= kMaxLookups) return fail(-1, "lookup table full (CUFHE_AMD_MAX_LOOKUPS definitions until CleanUp)");
-    g_lookup[k] = LookupDef{{coeffs[0], coeffs[1]}, offset, nout, s};
-    g_lookup_count.store(k + 1, std::memory_order_release);
-    *op = CUFHE_AMD_LOOKUP_OP_BASE + k;
-    return 0;
+    // a lookup's table comes with each call: there is no row to write
+    return define_op(g_ops.lookup, LookupDef{{coeffs[0], coeffs[1]}, offset, nout, s}, [](int i) { return g_dev[i].keys_ready; },
+                     "Initialize(ek) has not been called for every device", "lookup table full (CUFHE_AMD_MAX_LOOKUPS definitions until CleanUp)",
+                     false, [](int, int) { return 0; }, op);
 }
 
 int cufhe_amd_enqueue_lookup(int device, void* stream, int op, int copying, int nout, cufhe_amd_ctxt* const* outs, cufhe_amd_ctxt* table,
@@ -244,8 +198,8 @@ int cufhe_amd_enqueue_lookup(int device, void* stream, int op, int copying, int 
     if (g_param_set >= 0) return fail_lut_set();
     if (g_lvl0_ring == 2048) return fail(-1, "enqueue_lookup: lookups run on the default path only: not on the N = 2048 ring (\"lvl0_ring\")");
     if (int rc = check_device(device)) return rc;
-    const LookupDef* d = lookup_def(op);
-    if (!d || lookup_output(op) != 0) return fail(-1, "enqueue_lookup: op must be a defined lookup (cufhe_amd_define_lookup; its output-0 id)");
+    const LookupDef* d = g_ops.lookup.find(op);
+    if (!d || kLookupOps.output(op) != 0) return fail(-1, "enqueue_lookup: op must be a defined lookup (cufhe_amd_define_lookup; its output-0 id)");
     if (nout != d->nout) return fail(-1, "enqueue_lookup: nout must be the definition's output count");
     if (!outs || !table || !in0) return fail(-1, "enqueue_lookup: null ciphertext");
     if (d->c[1] != 0 && !in1) return fail(-1, "enqueue_lookup: the definition needs a second address operand");

@@ -132,14 +132,11 @@ struct Lvl2Path {
     using Mid = uint64_t;
     static constexpr int lvl0_words = kLvl0Words, mid_words = k2Words, n = kLvl0N;
     static constexpr uint64_t ks_mu = k2Mu;
-    static constexpr bool lvl1_gates = false, user_gates = false, lvl2_user_gates = true;
+    static constexpr bool lvl1_gates = false, rotate_takes_tv_rows = true;
+    // the ring's own definitions (cufhe_amd_lvl2_define_gate) alone run here: the registry's rule
+    static constexpr opreg::Path path = opreg::Path::Ring;
     static constexpr int set_index = -1;
-    // the ring's own definitions (cufhe_amd_lvl2_define_gate): an op of cufhe_amd_define_gate stays refused here
-    static const UserGate* user_op(int op) { return lvl2_user_gate(op); }
-    static uint32_t tv_pad(int op, const UserGate& u) { return u.tv ? make_pad2(lvl2_user_def(op), 0) : 0u; }
-    static int user_def(int op) { return lvl2_user_def(op); }
-    static int user_output(int op) { return lvl2_user_output(op); }
-    static uint32_t multi_pad(int op, const UserGate& u) { return make_pad2(lvl2_user_def(op), u.s); }
+    static constexpr uint32_t pad(int row, int s) { return make_pad2(row, s); }
     DeviceState& s;
     int ready() const { return s.keys2_ready ? 0 : fail(-3, "cufhe_amd_lvl2_initialize has not been called for this device"); }
     int rotate(hipStream_t st, const RotDesc2* d, size_t count, int steps, uint64_t* dump, bool tv_rows) const { return launch_blind_rotate_lvl2(s, st, d, count, steps, dump, tv_rows); }
@@ -163,17 +160,15 @@ int lvl2_user_rotations(int device, void* stream, size_t count, int op, const ui
 {
     if (int rc = use_device(device)) return rc;
     DeviceState& s = g_dev[device];
-    if (!is_lvl2_user_op(op)) return fail(-1, "op is not in the lvl2 user gates' id range (CUFHE_AMD_LVL2_USER_OP_BASE + k)");
-    if (g_param_set >= 0) return fail_lvl2_user_path();
-    const UserGate* u = lvl2_user_gate(op);
-    if (!u) return fail_lvl2_user_op(op);
-    const int out_j = lvl2_user_output(op);
+    const opreg::Admission adm = opreg::admit(g_ops, op, opreg::Route{opreg::Path::Ring, -1, 0, g_param_set >= 0}, opreg::Entry::Lvl2Hook);
+    if (!adm) return refuse(adm.refusal);
+    const UserGate* u = adm.gate;
+    const int out_j = adm.j;
     if (acc && out_j != 0) return fail(-1, "the accumulator of a multi-output definition is dumped under output 0's id");
     if (!s.keys2_ready) return fail(-3, "cufhe_amd_lvl2_initialize has not been called for this device");
     if (!in0 || (!acc && !tlwe2)) return fail(-1, "null pointer");
+    if (const char* missing = opreg::missing_operand(*u, in1 != nullptr, in2 != nullptr)) return fail(-1, missing);
     const int arity = user_gate_arity(*u);
-    if (arity >= 2 && !in1) return fail(-1, "user gate needs a second operand");
-    if (arity == 3 && !in2) return fail(-1, "user gate needs a third operand");
     if (count == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     Scratch sc;
@@ -187,20 +182,14 @@ int lvl2_user_rotations(int device, void* stream, size_t count, int op, const ui
     uint64_t* all = nullptr;          // a multi-output definition: [count][nout][N2 + 1], of which output out_j reaches tlwe2
     if (multi_bytes)
         if (int rc = sc.alloc((void**)&all, multi_bytes)) return rc;
-    const uint32_t pad = multi ? Lvl2Path::multi_pad(op, *u) : Lvl2Path::tv_pad(op, *u);
+    const uint32_t pad = u->tv ? Lvl2Path::pad(adm.k, u->s) : 0u;
     std::vector<RotDesc2> rot(count);
     std::vector<LinDesc> pre;
     for (size_t g = 0; g < count; g++) {
-        const uint32_t* a = in0 + g * kLvl0Words;
-        const uint32_t* b = arity >= 2 ? in1 + g * kLvl0Words : a;
-        int32_t ca = u->c[0], cb = u->c[1];
-        if (arity == 3) {
-            uint32_t* t = tmpp + g * kLvl0Words;
-            pre.push_back({a, b, t, u->c[0], u->c[1], 0u, 0u});
-            a = t; b = in2 + g * kLvl0Words; ca = 1; cb = u->c[2];
-        }
+        const size_t w = g * kLvl0Words;
+        const opreg::GateOperands x = opreg::user_gate_operands(*u, in0 + w, in1 ? in1 + w : nullptr, in2 ? in2 + w : nullptr, [&] { return tmpp + w; }, pre);
         uint64_t* o = !tlwe2 ? nullptr : multi ? all + g * (size_t)u->nout * k2Words : tlwe2 + g * k2Words;
-        rot[g] = RotDesc2{a, b, o, ca, cb, u->off, pad};
+        rot[g] = RotDesc2{x.a, x.b, o, x.ca, x.cb, u->off, pad};
     }
     RotDesc2* drot;
     LinDesc* dpre;
@@ -294,31 +283,20 @@ int cufhe_amd_lvl2_gate_batch(int device, void* stream, size_t count, const int3
     });
 }
 
-// definition k = g_user2_count of a lvl2 user gate with nout = 2^sh outputs (1: cufhe_amd_lvl2_define_gate); the caller holds g_mu
+// a lvl2 user gate with nout = 2^sh outputs (1: cufhe_amd_lvl2_define_gate); the caller holds g_mu
 static int define_lvl2_user_gate(const int32_t coeffs[3], uint32_t offset, const uint64_t* test_vector, int sh, int* op)
 {
     if (!coeffs || !op) return fail(-1, "null pointer");
     if (coeffs[0] == 0) return fail(-1, "lvl2 user gate: c0 must not be 0");
     if (g_param_set >= 0) return fail(-1, "lvl2 user gates run on the N = 2048 ring only: not while \"param_set\" is active");
-    for (int i = 0; i < g_gpu_num; i++)
-        if (!g_dev[i].keys2_ready) return fail(-3, "cufhe_amd_lvl2_initialize has not been called for every device");
-    const int k = g_user2_count.load(std::memory_order_relaxed);
-    if (k >= kMaxUserGates2) return fail(-1, "lvl2 user gate table full (CUFHE_AMD_LVL2_MAX_USER_GATES definitions until CleanUp)");
-    // every device's table exists before any row is written; row k of every table is written synchronously, and no launch reads the
-    // row before its id exists
-    for (int i = 0; i < g_gpu_num; i++) {
-        HIP_TRY(hipSetDevice(phys_device(i)));
-        if (int rc = ensure_tvs2(g_dev[i])) return rc;
-    }
-    if (test_vector)
-        for (int i = 0; i < g_gpu_num; i++) {
-            HIP_TRY(hipSetDevice(phys_device(i)));
-            HIP_TRY(hipMemcpy(g_dev[i].tvs2 + (size_t)k * k2N, test_vector, k2N * sizeof(uint64_t), hipMemcpyHostToDevice));
-        }
-    g_user2[k] = UserGate{{coeffs[0], coeffs[1], coeffs[2]}, offset, test_vector != nullptr, 1 << sh, sh};
-    g_user2_count.store(k + 1, std::memory_order_release);
-    *op = CUFHE_AMD_LVL2_USER_OP_BASE + k;
-    return 0;
+    // the ring's table holds the library's own rows too, so it exists on every device whether or not this definition has a test vector
+    return define_op(g_ops.lvl2, make_user_gate(coeffs, offset, test_vector != nullptr, sh), [](int i) { return g_dev[i].keys2_ready; },
+                     "cufhe_amd_lvl2_initialize has not been called for every device",
+                     "lvl2 user gate table full (CUFHE_AMD_LVL2_MAX_USER_GATES definitions until CleanUp)",
+                     true, [&](int i, int k) {
+                         if (int rc = ensure_tvs2(g_dev[i])) return rc;
+                         return test_vector ? write_tv_row(&g_dev[i].tvs2, kTvRows2, k2N, k, test_vector) : 0;
+                     }, op);
 }
 
 int cufhe_amd_lvl2_define_gate(const int32_t coeffs[3], uint32_t offset, const uint64_t* test_vector, int* op)

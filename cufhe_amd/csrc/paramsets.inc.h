@@ -136,15 +136,11 @@ struct PsPath {
     using Mid = uint32_t;
     static constexpr int lvl0_words = D::lvl0_words, mid_words = D::lvl1_words, n = PS::n;
     static constexpr uint32_t ks_mu = kMu;
-    static constexpr bool lvl1_gates = true, has_cmux = !PS::small_modulus, user_gates = true, packed_rom = false, lvl2_user_gates = false;
-    // the set's own definitions (cufhe_amd_ps_define_gate made for this set): ids of cufhe_amd_define_gate, of cufhe_amd_lvl2_define_gate
-    // and of another set's definitions stay refused here (lower_gates)
+    static constexpr bool lvl1_gates = true, has_cmux = !PS::small_modulus, packed_rom = false, rotate_takes_tv_rows = true;
+    // the definitions made for this set (cufhe_amd_ps_define_gate) alone run here: the registry's rule
+    static constexpr opreg::Path path = opreg::Path::Set;
     static constexpr int set_index = ps_index_of<PS>();
-    static const UserGate* user_op(int op) { return ps_user_gate(op, set_index); }
-    static int user_def(int op) { return ps_user_def(op); }
-    static int user_output(int op) { return ps_user_output(op); }
-    static uint32_t multi_pad(int op, const UserGate& u) { return make_pad(ps_user_def(op), u.s); }
-    static uint32_t tv_pad(int op, const UserGate& u) { return u.tv ? make_pad(ps_user_def(op), 0) : 0u; }
+    static constexpr uint32_t pad(int row, int s) { return make_pad(row, s); }
     static constexpr size_t trlwe_words = (size_t)D::K1 * D::N;
     static constexpr auto se_kernel = sample_extract_ps_kernel<PS>;
     DeviceState& s;
@@ -240,36 +236,18 @@ void ps_release(int device)
     }
 }
 
-// definition k = g_ps_user_count of a user gate of parameter set `set` with nout = 2^sh outputs (1: cufhe_amd_ps_define_gate); the
-// caller holds g_mu
+// a user gate of parameter set `set` with nout = 2^sh outputs (1: cufhe_amd_ps_define_gate); the caller holds g_mu
 int define_ps_user_gate(int set, const int32_t coeffs[3], uint32_t offset, const uint32_t* test_vector, int sh, int* op)
 {
     if (!coeffs || !op) return fail(-1, "null pointer");
     if (coeffs[0] == 0) return fail(-1, "parameter set user gate: c0 must not be 0");
     return ps_dispatch(set, [&](auto psx) -> int {
         constexpr size_t N = PsDims<decltype(psx)>::N;
-        for (int i = 0; i < g_gpu_num; i++)
-            if (!ps_state(set, i).ready) return fail(-3, "cufhe_amd_ps_initialize has not been called for this parameter set on every device");
-        const int k = g_ps_user_count.load(std::memory_order_relaxed);
-        if (k >= kMaxUserGates) return fail(-1, "parameter set user gate table full (CUFHE_AMD_PS_MAX_USER_GATES definitions until CleanUp)");
-        if (test_vector) {
-            // row k of the set's table on every device, synchronously (like the key replicas); no launch reads the row before its id exists
-            for (int i = 0; i < g_gpu_num; i++) {
-                PsState& ps = ps_state(set, i);
-                HIP_TRY(hipSetDevice(phys_device(i)));
-                if (!ps.tvs) {
-                    DevPtr<uint32_t> t;
-                    HIP_TRY(t.alloc((size_t)kMaxUserGates * N));
-                    ps.tvs = t.release();
-                }
-                HIP_TRY(hipMemcpy(ps.tvs + (size_t)k * N, test_vector, N * sizeof(uint32_t), hipMemcpyHostToDevice));
-            }
-        }
-        g_ps_user[k] = UserGate{{coeffs[0], coeffs[1], coeffs[2]}, offset, test_vector != nullptr, 1 << sh, sh};
-        g_ps_user_set[k] = set;
-        g_ps_user_count.store(k + 1, std::memory_order_release);
-        *op = CUFHE_AMD_PS_USER_OP_BASE + k;
-        return 0;
+        return define_op(g_ops.ps, opreg::PsUserGate{make_user_gate(coeffs, offset, test_vector != nullptr, sh), set},
+                         [&](int i) { return ps_state(set, i).ready; },
+                         "cufhe_amd_ps_initialize has not been called for this parameter set on every device",
+                         "parameter set user gate table full (CUFHE_AMD_PS_MAX_USER_GATES definitions until CleanUp)",
+                         test_vector != nullptr, [&](int i, int k) { return write_tv_row(&ps_state(set, i).tvs, kMaxUserGates, N, k, test_vector); }, op);
     });
 }
 
@@ -463,16 +441,15 @@ int cufhe_amd_ps_user_rotate(int set, int device, void* stream, size_t count, in
         using PS = decltype(psx);
         using P = PsPath<PS>;
         constexpr size_t w0 = P::lvl0_words;
-        if (!is_ps_user_op(op)) return fail(-1, "op is not in the parameter sets' user gate id range (CUFHE_AMD_PS_USER_OP_BASE + k)");
-        const UserGate* u = ps_user_gate(op, set);
-        if (!u) return fail_ps_user_op(op, set);
-        if (ps_user_output(op) != 0) return fail(-1, "the accumulator of a multi-output definition is dumped under output 0's id");
+        const opreg::Admission adm = opreg::admit(g_ops, op, opreg::Route{opreg::Path::Set, set, 0, g_param_set >= 0}, opreg::Entry::PsHook);
+        if (!adm) return refuse(adm.refusal);
+        const UserGate* u = adm.gate;
+        if (adm.j != 0) return fail(-1, "the accumulator of a multi-output definition is dumped under output 0's id");
         const P p{g_dev[device], ps_state(set, device)};
         if (int rc = p.ready()) return rc;
         if (!in0 || !acc) return fail(-1, "null pointer");
+        if (const char* missing = opreg::missing_operand(*u, in1 != nullptr, in2 != nullptr)) return fail(-1, missing);
         const int arity = user_gate_arity(*u);
-        if (arity >= 2 && !in1) return fail(-1, "user gate needs a second operand");
-        if (arity == 3 && !in2) return fail(-1, "user gate needs a third operand");
         if (count == 0) return 0;
         hipStream_t st = (hipStream_t)stream;
         Scratch sc;
@@ -480,18 +457,12 @@ int cufhe_amd_ps_user_rotate(int set, int device, void* stream, size_t count, in
         uint32_t* tmpp = nullptr;
         if (arity == 3)
             if (int rc = sc.alloc((void**)&tmpp, count * w0 * sizeof(uint32_t))) return rc;
-        const uint32_t pad = u->nout > 1 ? P::multi_pad(op, *u) : P::tv_pad(op, *u);
+        const uint32_t pad = u->tv ? P::pad(adm.k, u->s) : 0u;
         std::vector<LinDesc> rot(count), pre;
         for (size_t g = 0; g < count; g++) {
-            const uint32_t* a = in0 + g * w0;
-            const uint32_t* b = arity >= 2 ? in1 + g * w0 : a;
-            int32_t ca = u->c[0], cb = u->c[1];
-            if (arity == 3) {
-                uint32_t* t = tmpp + g * w0;
-                pre.push_back({a, b, t, u->c[0], u->c[1], 0u, 0u});
-                a = t; b = in2 + g * w0; ca = 1; cb = u->c[2];
-            }
-            rot[g] = LinDesc{a, b, nullptr, ca, cb, u->off, pad};
+            const size_t w = g * w0;
+            const opreg::GateOperands x = opreg::user_gate_operands(*u, in0 + w, in1 ? in1 + w : nullptr, in2 ? in2 + w : nullptr, [&] { return tmpp + w; }, pre);
+            rot[g] = LinDesc{x.a, x.b, nullptr, x.ca, x.cb, u->off, pad};
         }
         LinDesc *drot, *dpre;
         if (int rc = upload_descs(p.s, sc, rot, &drot)) return rc;

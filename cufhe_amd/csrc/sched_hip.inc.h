@@ -22,13 +22,10 @@ long g_sched_zero_copy = 1;       // 1: ciphertext staging is read / written by 
 long g_sched_affinity = 1;        // 1: a device's launch worker runs on the CPUs local to that GPU (NUMA node of its PCI function)
 
 // The recorded lookups, Spreads and table rotations (lut.inc.h): their op ids are split off a level's gate list and lowered there
-constexpr int kMaxLookups = 64;
-struct LookupDef { int32_t c[2]; uint32_t off; int nout; int s; };      // x = c0 in0 + c1 in1 + (0, .., 0, off), nout = 2^s outputs
+using opreg::LookupDef;
 bool is_lut_op(int op);
 bool is_spread_op(int op);
-const LookupDef* lookup_def(int op);      // of a lookup OUTPUT id (nullptr: none)
 int lower_lut_ops(DeviceState& s, hipStream_t st, const GateRef* g, size_t n);
-void lut_forget_definitions();
 // The recorded packs (pack.inc.h): split off a level's TRLWE-kind list in the same way
 int lower_pack_ops(DeviceState& s, hipStream_t st, const GateRef* g, size_t n);
 bool is_split_op(int op) { return op == CUFHE_AMD_TL_PACK || is_lut_op(op); }
@@ -175,8 +172,8 @@ class HipBackend : public sched::Backend {
     }
     bool shares_rotation(int op) override
     {
-        if (const LookupDef* d = lookup_def(op)) return d->nout > 1;
-        const UserGate* u = user_gate(op);
+        if (const LookupDef* d = g_ops.lookup.find(op)) return d->nout > 1;
+        const UserGate* u = g_ops.user.find(op);
         return u && u->nout > 1;
     }
     int lowering(int op) override { return is_split_op(op) ? 1 : 0; }
@@ -399,7 +396,7 @@ int sched_synchronize_all()
 void sched_quiesce(bool cleanup = true)
 {
     if (g_scheduler) (void)g_scheduler->synchronize_all();
-    if (cleanup) lut_forget_definitions();     // lookup ids count from the last cufhe_amd_cleanup; whatever was recorded with them has run
+    if (cleanup) g_ops.lookup.clear();     // lookup ids count from the last cufhe_amd_cleanup; whatever was recorded with them has run
     if (!g_scheduler) return;
     for (int d = 0; d < g_scheduler->gpu_num(); d++) {
         g_scheduler->dev(d).backend()->bind_thread();
@@ -479,26 +476,13 @@ int cufhe_amd_enqueue_gate(int device, void* stream, int op, int copying, cufhe_
 {
     std::lock_guard<std::mutex> lk(g_sched_mu);
     if (int rc = check_device(device)) return rc;
-    const UserGate* u = user_gate(op);     // a user gate: an ordinary gate of one, two or three operands, kind = its output level
-    if (is_user_op(op) && !u) return fail_user_op(op);
-    // a lvl2 user gate (cufhe_amd_lvl2_define_gate): the same, for lvl0 ciphertexts while they bootstrap through the N = 2048 ring
-    const bool u2 = is_lvl2_user_op(op);
-    if (u2) {
-        if (!out || !in0) return fail(-1, "null ciphertext");
-        if (g_param_set >= 0 || g_lvl0_ring != 2048 || out->level != 0) return fail_lvl2_user_path();
-        if (!(u = lvl2_user_gate(op))) return fail_lvl2_user_op(op);
-    }
-    // a user gate of a parameter set (cufhe_amd_ps_define_gate): the same, at either level, while "param_set" is the set it was made for
-    const bool ups = is_ps_user_op(op);
-    if (ups) {
-        if (!out || !in0) return fail(-1, "null ciphertext");
-        if (g_param_set < 0 || (g_lvl0_ring == 2048 && out->level == 0)) return fail_ps_user_path();
-        if (!(u = ps_user_gate(op, (int)g_param_set))) return fail_ps_user_op(op, (int)g_param_set);
-    }
+    // a user gate of any family is an ordinary gate of one, two or three operands, kind = its output level, where its family runs
+    const opreg::Admission a = opreg::admit(g_ops, op, opreg::route_of_options(g_param_set, g_lvl0_ring, out ? out->level : -1),
+                                            opreg::Entry::Recorded, out && in0);
+    if (!a) return refuse(a.refusal);
+    const UserGate* u = a.gate;
     if (!u && (op < 0 || op >= CUFHE_AMD_NUM_OPS)) return fail(-1, "unknown gate op");
     if (!out || !in0) return fail(-1, "null ciphertext");
-    if (u && !u2 && !ups && (g_param_set >= 0 || (g_lvl0_ring == 2048 && out->level == 0)))
-        return fail(-1, "user gates run on the default path only: not with \"param_set\" active or on the N = 2048 ring (\"lvl0_ring\")");
     const bool three = op == CUFHE_AMD_MUX || op == CUFHE_AMD_NMUX || (u && user_gate_arity(*u) == 3);
     const bool one = op == CUFHE_AMD_NOT || op == CUFHE_AMD_COPY || (u && user_gate_arity(*u) == 1);
     if (!one && !in1) return fail(-1, "gate needs a second operand");
@@ -523,20 +507,16 @@ int cufhe_amd_enqueue_gate_multi(int device, void* stream, int op, int copying, 
 {
     std::lock_guard<std::mutex> lk(g_sched_mu);
     if (int rc = check_device(device)) return rc;
-    if (is_lvl2_user_op(op)) return fail(-1, "enqueue_gate_multi: lvl2 user gates have one output (cufhe_amd_enqueue_gate)");
-    if (is_ps_user_op(op))
-        return fail(-1, "enqueue_gate_multi: the outputs of a parameter set's user gate are recorded one by one (cufhe_amd_enqueue_gate with "
-                        "CUFHE_AMD_PS_USER_OP_OUTPUT(op, j)); siblings on the same operands in one flush share the rotation");
-    const UserGate* u = user_gate(op);
-    if (is_user_op(op) && !u) return fail_user_op(op);
-    if (!u || user_output(op) != 0 || u->nout < 2) return fail(-1, "enqueue_gate_multi: op must be a multi-output user gate (cufhe_amd_define_gate_multi)");
+    // the route is asked last, after the checks of the call's own arguments
+    const opreg::Admission a = opreg::admit(g_ops, op, opreg::Route{}, opreg::Entry::RecordedMulti);
+    if (!a) return refuse(a.refusal);
+    const UserGate* u = a.gate;
+    if (!u || a.j != 0 || u->nout < 2) return fail(-1, "enqueue_gate_multi: op must be a multi-output user gate (cufhe_amd_define_gate_multi)");
     if (nout != u->nout) return fail(-1, "enqueue_gate_multi: nout must be the definition's output count");
     if (!outs || !in0) return fail(-1, "null ciphertext");
-    if (g_param_set >= 0 || (g_lvl0_ring == 2048 && outs[0] && outs[0]->level == 0))
-        return fail(-1, "user gates run on the default path only: not with \"param_set\" active or on the N = 2048 ring (\"lvl0_ring\")");
+    if (int rc = refuse(opreg::routed(a.family, opreg::route_of_options(g_param_set, g_lvl0_ring, outs[0] ? outs[0]->level : -1)))) return rc;
+    if (const char* missing = opreg::missing_operand(*u, in1 != nullptr, in2 != nullptr)) return fail(-1, missing);
     const int arity = user_gate_arity(*u);
-    if (arity >= 2 && !in1) return fail(-1, "user gate needs a second operand");
-    if (arity == 3 && !in2) return fail(-1, "user gate needs a third operand");
     cufhe_amd_ctxt* ins[3] = {in0, arity >= 2 ? in1 : nullptr, arity == 3 ? in2 : nullptr};
     sched::Scheduler* S = scheduler();
     int ops[1 << kMaxOutputShift];
