@@ -197,7 +197,18 @@ SIGNATURES = {
     "cufhe_amd_enqueue_lut_rotate": (ctypes.c_int, [ctypes.c_int, c_void, ctypes.c_int, ctypes.c_int, c_void, c_void, c_void]),
 }
 
-for _name, (_res, _args) in SIGNATURES.items():
+# ... and every symbol include/cufhe_amd_linear.h declares (the part of the header that holds the linear layers)
+LINEAR_SIGNATURES = {
+    "cufhe_amd_linear_define": (ctypes.c_int, [ctypes.c_size_t, ctypes.c_size_t, c_void, c_void, ctypes.POINTER(ctypes.c_int)]),
+    "cufhe_amd_linear_get": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)]),
+    "cufhe_amd_linear_batch": (ctypes.c_int, [ctypes.c_int, c_void, ctypes.c_int, ctypes.c_int, ctypes.c_size_t, c_void, ctypes.c_size_t,
+                                              c_void, ctypes.c_size_t]),
+    "cufhe_amd_linear_list": (ctypes.c_int, [ctypes.c_int, c_void, ctypes.c_int, ctypes.c_int, ctypes.c_size_t, c_void, c_void]),
+    "cufhe_amd_linear_gate_batch": (ctypes.c_int, [ctypes.c_int, c_void, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_size_t, c_void,
+                                                   ctypes.c_size_t, c_void, ctypes.c_size_t]),
+}
+
+for _name, (_res, _args) in list(SIGNATURES.items()) + list(LINEAR_SIGNATURES.items()):
     _fn = getattr(lib, _name)          # AttributeError here = the .so is stale: rebuild
     _fn.restype = _res
     _fn.argtypes = _args

@@ -820,6 +820,57 @@ def Pack(out_trlwe, ins, positions, st):
     _pack(True, out_trlwe, ins, positions, st)
 
 
+# ---- linear layers: an integer matrix times a vector of ciphertexts ----
+class LinearLayer:
+    """a layer id of cufhe_amd_linear_define with its shape; valid until CleanUp"""
+
+    def __init__(self, layer_id, rows, cols):
+        self.id, self.rows, self.cols = int(layer_id), int(rows), int(cols)
+
+
+def define_linear(W, bias=None):
+    """W: [rows][cols] integers that fit int32; bias: rows torus words (uint32) or None for zeros.  The weights are copied to every
+    device of SetGPUNum before the call returns.  Noise (variance times sum_k W[j][k]^2) and the padding bit are the caller's concern."""
+    w = np.asarray(W)
+    assert w.ndim == 2 and w.size and np.issubdtype(w.dtype, np.integer)
+    assert w.min() >= -(1 << 31) and w.max() < (1 << 31), "weights are int32"
+    w = np.ascontiguousarray(w, dtype=np.int32)
+    b = None
+    if bias is not None:
+        b = np.ascontiguousarray(np.asarray(bias, dtype=np.uint64) & 0xFFFFFFFF, dtype=np.uint32)
+        assert b.shape == (w.shape[0],)
+    layer = ctypes.c_int(-1)
+    check(lib.cufhe_amd_linear_define(w.shape[0], w.shape[1], _ptr(w), _ptr(b) if b is not None else None, ctypes.byref(layer)))
+    return LinearLayer(layer.value, w.shape[0], w.shape[1])
+
+
+def _linear_strides(level, in_stride_words, out_stride_words):
+    words = lib.cufhe_amd_ctxt_words(level) if level in (0, 1) else 1     # a bad level is rejected by the library
+    return (words if in_stride_words is None else in_stride_words), (words if out_stride_words is None else out_stride_words)
+
+
+def linear_batch(layer, level, out, inp, sets, device=0, stream=None, in_stride_words=None, out_stride_words=None):
+    """out[s rows + j] = sum_k W[j][k] inp[s cols + k] + (0, .., 0, bias[j]) mod 2^32 on DeviceBuffers of `sets` input vectors; strides
+    in words from one ciphertext to the next (default: packed).  Not recorded: Stream.fence() orders it behind recorded gates."""
+    si, so = _linear_strides(level, in_stride_words, out_stride_words)
+    check(lib.cufhe_amd_linear_batch(device, stream, layer.id, level, sets, inp.ptr, si, out.ptr, so))
+
+
+def linear_list(layer, level, outs, ins, sets, device=0, stream=None):
+    """the same on lists of device pointers (ints): ins[s cols + k], outs[s rows + j]; operands are read where they lie"""
+    assert len(ins) == sets * layer.cols and len(outs) == sets * layer.rows
+    a = (ctypes.c_void_p * max(len(ins), 1))(*ins)
+    o = (ctypes.c_void_p * max(len(outs), 1))(*outs)
+    check(lib.cufhe_amd_linear_list(device, stream, layer.id, level, sets, a, o))
+
+
+def linear_gate_batch(layer, op, level, out, inp, sets, device=0, stream=None, in_stride_words=None, out_stride_words=None):
+    """linear_batch into a temporary of the library, then the one-input user gate `op` (define_gate with c1 = c2 = 0, or an output id of
+    such a multi-output definition) on each of the sets * rows sums: a fully connected layer with the gate's test vector as activation."""
+    si, so = _linear_strides(level, in_stride_words, out_stride_words)
+    check(lib.cufhe_amd_linear_gate_batch(device, stream, layer.id, int(op), level, sets, inp.ptr, si, out.ptr, so))
+
+
 def polymul512_batch(a, b, res, count, device=0, stream=None):
     check(lib.cufhe_amd_polymul512_batch(device, stream, count, a.ptr, b.ptr, res.ptr))
 

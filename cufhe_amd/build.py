@@ -13,8 +13,8 @@ LL_FLAGS = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
 # blind_rotate_kernel 35.69 -> 35.34 ms per 4096 rotations, the N = 512 parameter-set kernel 33.7 -> 32.8 ms, everything else within 0.2 %;
 # max-ilp here: 36.26 ms)
 MAIN_FLAGS = ["-mllvm", "-amdgpu-sched-strategy=max-memory-clause"]
-DEPS = [os.path.join(HERE, "csrc", f) for f in ("capi.hip", "kernels_ll.hip", "kernels_common.hip.h", "kernels.hip.h", "kernels_lvl2.hip.h", "kernels_lvl2q.hip.h", "kernels_ks2.hip.h", "kernels_pks.hip.h", "cb.inc.h", "kernels_pack.hip.h", "pack.inc.h", "kernels_lut.hip.h", "lut.inc.h", "kernels_ll.hip.h", "kernels_ps.hip.h", "paramsets.inc.h", "ntt_wave512.h", "lvl2.inc.h", "sched_hip.inc.h", "sched_core.h", "launch_plan.h", "op_registry.h", "ks_matrix.h", "ntt_wave.h", "ntt_r4.h", "ntt_tables.h", "fpfield.h")] + \
-       [os.path.join(os.path.dirname(HERE), "include", "cufhe_amd.h")]
+DEPS = [os.path.join(HERE, "csrc", f) for f in ("capi.hip", "kernels_ll.hip", "kernels_common.hip.h", "kernels.hip.h", "kernels_lvl2.hip.h", "kernels_lvl2q.hip.h", "kernels_ks2.hip.h", "kernels_pks.hip.h", "cb.inc.h", "kernels_pack.hip.h", "pack.inc.h", "kernels_lut.hip.h", "lut.inc.h", "kernels_linear.hip.h", "linear.inc.h", "kernels_ll.hip.h", "kernels_ps.hip.h", "paramsets.inc.h", "ntt_wave512.h", "lvl2.inc.h", "sched_hip.inc.h", "sched_core.h", "launch_plan.h", "op_registry.h", "ks_matrix.h", "ntt_wave.h", "ntt_r4.h", "ntt_tables.h", "fpfield.h")] + \
+       [os.path.join(os.path.dirname(HERE), "include", f) for f in ("cufhe_amd.h", "cufhe_amd_linear.h")]
 OUT = os.path.join(HERE, "libcufhe_amd.so")
 # -ffp-contract=off: the field arithmetic spells out every fma; nothing may be re-fused
 FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-std=c++17"]

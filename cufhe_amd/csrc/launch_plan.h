@@ -2,7 +2,7 @@
 // Host only, standard library only, no allocation: capi.hip and its .inc.h files turn the plans into launches, the scheduler's
 // backend (sched_hip.inc.h) prices its levels with the same plans, and tests/host/launch_plan_harness.cpp prints them on the CPU
 // (tests/test_launch_plan.py: the plans of the code this header replaced, tests/golden/launch_plans_v1.json; plan_pack:
-// tests/host/plan_pack_harness.cpp, tests/test_pack.py).
+// tests/host/plan_pack_harness.cpp, tests/test_pack.py; plan_linear: tests/host/plan_linear_harness.cpp, tests/test_linear.py).
 //
 // Every rule is in units of the device's CU count (MI355X: 256; the measured milliseconds in the comments are that chip's).
 #pragma once
@@ -287,6 +287,46 @@ inline PackPlan plan_pack(size_t count, int cus, PackGeometry g, const Tuning& t
     else if (wgs > 0 && wgs < want) slices = (want + wgs - 1) / wgs;
     slices = std::max(1L, std::min<long>(slices, max_slices));
     return {tiles, (int)slices, (unsigned)wgs, (unsigned)slices};
+}
+
+// ---- linear layers ----
+
+// Launch shape of linear_kernel (kernels_linear.hip.h): y[set][row] = sum_k W[row][k] x[set][k] (+ bias) on ciphertexts of `words` words.
+// A lane owns one word index, a wave 64 consecutive ones (a chunk; the last chunk of a ciphertext is partial: 631 and 1025 are no
+// multiples of 64) of one set and a tile of kLinearRowTile rows held in registers; it walks k in steps of kLinearUnroll.  Waves are
+// numbered row tile first, then chunk, then set, so the waves of a workgroup read the same input words (one trip to L2 per workgroup,
+// the others hit the CU's vector cache) and the workgroups in flight share few chunks.  Four waves per workgroup; a launch with fewer
+// such workgroups than CUs runs one wave per workgroup instead, so that a small layer still spreads over the device.
+constexpr int kLinearRowTile = 16;       // TJ: rows per wave, one accumulator register each
+constexpr int kLinearUnroll = 4;         // U: inputs loaded before their products are formed
+constexpr int kLinearWaveWords = 64;
+constexpr int kLinearMaxWaves = 4;
+struct LinearPlan {
+    int row_tile, unroll;          // kLinearRowTile, kLinearUnroll: what the tests take their boundaries from
+    int row_tiles, chunks;         // tiles of rows per set, chunks of 64 words per ciphertext
+    long waves;                    // sets * chunks * row_tiles
+    int waves_per_block;           // 4 or 1
+    unsigned grid_x, block_x;      // ceil(waves / waves_per_block) workgroups of 64 * waves_per_block threads
+};
+// the wave's place in the plan, and register j / lane l of it: the kernel and tests/host/plan_linear_harness.cpp both read the plan
+// through these
+constexpr long linear_wave_of(long block, int wave_in_block, int waves_per_block) { return block * waves_per_block + wave_in_block; }
+constexpr int linear_wave_tile(long wave, int row_tiles) { return (int)(wave % row_tiles); }
+constexpr int linear_wave_chunk(long wave, int row_tiles, int chunks) { return (int)(wave / row_tiles % chunks); }
+constexpr long linear_wave_set(long wave, int row_tiles, int chunks) { return wave / row_tiles / chunks; }
+constexpr int linear_row(int tile, int j) { return tile * kLinearRowTile + j; }                 // live when < rows
+constexpr int linear_word(int chunk, int lane) { return chunk * kLinearWaveWords + lane; }      // live when < words
+inline LinearPlan plan_linear(size_t rows, size_t cols, size_t sets, int words, int cus)
+{
+    (void)cols;      // the walk over k is inside a wave: it changes no shape
+    LinearPlan p{kLinearRowTile, kLinearUnroll, 0, 0, 0, kLinearMaxWaves, 0, 0};
+    p.row_tiles = (int)((rows + kLinearRowTile - 1) / kLinearRowTile);
+    p.chunks = (words + kLinearWaveWords - 1) / kLinearWaveWords;
+    p.waves = (long)sets * p.chunks * p.row_tiles;
+    if ((p.waves + kLinearMaxWaves - 1) / kLinearMaxWaves < (long)device_cus(cus)) p.waves_per_block = 1;
+    p.grid_x = (unsigned)((p.waves + p.waves_per_block - 1) / p.waves_per_block);
+    p.block_x = (unsigned)(kLinearWaveWords * p.waves_per_block);
+    return p;
 }
 
 }  // namespace plan

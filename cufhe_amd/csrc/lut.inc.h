@@ -339,3 +339,6 @@ int cufhe_amd_trlwe_spread_batch(int device, void* stream, size_t count, const u
 }
 
 }  // extern "C"
+
+// linear layers: the one leveled operation on TLWEs, in front of the gates and lookups above
+#include "linear.inc.h"

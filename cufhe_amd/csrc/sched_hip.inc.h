@@ -391,12 +391,15 @@ int sched_synchronize_all()
     return 0;
 }
 
+void linear_drop_all();      // linear.inc.h
+
 // CleanUp: everything recorded completes, cached staging buffers and the internal streams go; the
 // scheduler itself (ciphertext slabs, workers) stays for the ciphertexts that outlive CleanUp.
 void sched_quiesce(bool cleanup = true)
 {
     if (g_scheduler) (void)g_scheduler->synchronize_all();
     if (cleanup) g_ops.lookup.clear();     // lookup ids count from the last cufhe_amd_cleanup; whatever was recorded with them has run
+    if (cleanup) linear_drop_all();        // so do the ids of linear layers; their device copies go with them
     if (!g_scheduler) return;
     for (int d = 0; d < g_scheduler->gpu_num(); d++) {
         g_scheduler->dev(d).backend()->bind_thread();

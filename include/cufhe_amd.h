@@ -674,6 +674,11 @@ int cufhe_amd_enqueue_lookup(int device, void* stream, int op, int copying, int 
 int cufhe_amd_enqueue_spread(int device, void* stream, int copying, cufhe_amd_ctxt* out, cufhe_amd_ctxt* in, int stride, int reps);
 int cufhe_amd_enqueue_lut_rotate(int device, void* stream, int copying, int nout, cufhe_amd_ctxt* out, cufhe_amd_ctxt* table, cufhe_amd_ctxt* addr);
 
+/* ---- linear layers: an integer matrix times a vector of ciphertexts ----
+ * cufhe_amd_linear_define, _linear_get, _linear_batch, _linear_list and _linear_gate_batch: declared and documented in
+ * cufhe_amd_linear.h, which this header includes. */
+#include "cufhe_amd_linear.h"
+
 /* ---- other parameter sets (CMakeLists.txt:8-24: USE_80BIT_SECURITY / USE_CGGI19 / USE_CONCRETE select TFHEpp
  * parameter headers at build time; k > 1: src/bootstrap_gpu.cu:402-421; N = 512: include/ntt_gpu/ntt_gpuntt.cuh:283-329)
  * Every set of cufhe_amd/csrc/kernels_ps.hip.h is compiled in and chosen by index: 0 = the default set (the same

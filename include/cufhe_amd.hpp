@@ -696,6 +696,64 @@ inline void gLookupTRLWE(const std::vector<Ctxt<TFHEpp::lvl0param>*>& outs, cons
     CUFHE_AMD_CHECK(rc);
 }
 
+/// Linear layers (include/cufhe_amd_linear.h): y_j = sum_k W[j][k] x_k + (0, .., 0, bias[j]) mod 2^32 on
+/// ciphertexts of one level -- with a one-input user gate behind it, an encrypted fully connected layer with an arbitrary activation.
+/// Exact word arithmetic, no key; the noise (the inputs' variance times sum_k W[j][k]^2) and the padding bit are the caller's concern.
+struct LinearLayer {
+    int id = -1;
+    size_t rows = 0, cols = 0;
+};
+/// W: rows x cols int32, row-major; bias: rows torus words or nullptr (zeros).  Copied to every device of SetGPUNum; valid until CleanUp.
+inline LinearLayer DefineLinear(size_t rows, size_t cols, const int32_t* W, const uint32_t* bias = nullptr)
+{
+    LinearLayer l;
+    CUFHE_AMD_CHECK(cufhe_amd_linear_define(rows, cols, W, bias, &l.id));
+    l.rows = rows; l.cols = cols;
+    return l;
+}
+/// *outs[j] = row j of the layer applied to *ins[0 .. cols): device buffers, read and written where they lie (no gather copy).  Like
+/// gPackTLWEs a BLOCKING form that is not recorded: the stream is fenced first and the call returns when the outputs are in their
+/// device buffers.  No output may be an input.
+template <class P>
+inline void gLinear(const std::vector<Ctxt<P>*>& outs, const LinearLayer& layer, const std::vector<Ctxt<P>*>& ins, Stream st)
+{
+    if (outs.size() != layer.rows || ins.size() != layer.cols) CUFHE_AMD_CHECK(-1);
+    const int dev = st.device_id();
+    CUFHE_AMD_CHECK(cufhe_amd_stream_fence(dev, st.raw()));
+    std::vector<const uint32_t*> src(ins.size());
+    std::vector<uint32_t*> dst(outs.size());
+    for (size_t k = 0; k < ins.size(); k++) src[k] = cufhe_amd_ctxt_device_ptr(ins[k]->handle, dev);
+    for (size_t j = 0; j < outs.size(); j++) dst[j] = cufhe_amd_ctxt_device_ptr(outs[j]->handle, dev);
+    CUFHE_AMD_CHECK(cufhe_amd_linear_list(dev, st.raw(), layer.id, detail::level_of<P>(), 1, src.data(), dst.data()));
+    CUFHE_AMD_CHECK(cufhe_amd_stream_synchronize(dev, st.raw()));
+}
+/// *outs[j] = gate(row j of the layer applied to *ins[0 .. cols)): the sums go to a temporary, then one launch sequence of outs.size()
+/// one-input user gates (DefineGate with coefficients {c0, 0, 0}, or Output(g, j) of such a multi-output gate) -- the words of
+/// cufhe_amd_linear_gate_batch.  Blocking and not recorded, like gLinear; an output may be an input.
+template <class P>
+inline void gLinearApply(UserGate gate, const std::vector<Ctxt<P>*>& outs, const LinearLayer& layer, const std::vector<Ctxt<P>*>& ins, Stream st)
+{
+    if (outs.size() != layer.rows || ins.size() != layer.cols) CUFHE_AMD_CHECK(-1);
+    const int dev = st.device_id(), level = detail::level_of<P>();
+    const size_t rows = outs.size(), words = (size_t)cufhe_amd_ctxt_words(level);
+    CUFHE_AMD_CHECK(cufhe_amd_stream_fence(dev, st.raw()));
+    void* sums = nullptr;
+    CUFHE_AMD_CHECK(cufhe_amd_malloc(dev, rows * words * sizeof(uint32_t), &sums));
+    std::vector<const uint32_t*> src(ins.size()), mid(rows);
+    std::vector<uint32_t*> tmp(rows), dst(rows);
+    for (size_t k = 0; k < ins.size(); k++) src[k] = cufhe_amd_ctxt_device_ptr(ins[k]->handle, dev);
+    for (size_t j = 0; j < rows; j++) {
+        mid[j] = tmp[j] = static_cast<uint32_t*>(sums) + j * words;
+        dst[j] = cufhe_amd_ctxt_device_ptr(outs[j]->handle, dev);
+    }
+    std::vector<int32_t> ops(rows, (int32_t)gate.op);
+    int rc = cufhe_amd_linear_list(dev, st.raw(), layer.id, level, 1, src.data(), tmp.data());
+    if (rc >= 0) rc = cufhe_amd_gate_list(dev, st.raw(), level, rows, ops.data(), dst.data(), mid.data(), nullptr, nullptr);
+    if (rc >= 0) rc = cufhe_amd_stream_synchronize(dev, st.raw());
+    (void)cufhe_amd_free(dev, sums);
+    CUFHE_AMD_CHECK(rc);
+}
+
 /// The recorded forms of the three ("Recorded forms"): scheduler nodes like the gates.  They return at once,
 /// are ordered by their operands, and all lookups, Spreads and table rotations of one dependence level share one launch sequence.
 /// DefineLookup: the address x = c0 in0 + c1 in1 + (0, .., 0, offset) is formed inside the rotation; nout = 1, 2, 4 or 8 outputs.
