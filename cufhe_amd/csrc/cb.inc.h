@@ -20,11 +20,11 @@ int launch_private_keyswitch(DeviceState& s, hipStream_t st, const uint64_t* in,
     if (count == 0) return 0;
     ProfScope prof{s, st, count, true};
     if (int rc = prof.begin()) return rc;
-    const auto [tiles, slices] = plan::plan_private_keyswitch(count, cus_of(s), {kPksTile, kPksChunks, kPksIn, kPksIBlock});
-    if (slices > 1)
+    const plan::PksPlan p = plan::plan_private_keyswitch(count, cus_of(s), kPksGeometry);
+    if (p.slices > 1)
         HIP_TRY(hipMemsetAsync(out, 0, (count / rows_per_out) * 2 * rows_per_out * kCbRowWords * sizeof(uint32_t), st));
-    hipLaunchKernelGGL(private_keyswitch_kernel, dim3((unsigned)(tiles * 2 * kPksChunks), (unsigned)slices), dim3(kPksThreads), 0, st,
-                       in, (int)count, s.cb_pksk, out, rows_per_out, tiles, slices);
+    hipLaunchKernelGGL(private_keyswitch_kernel, dim3(p.grid_x, p.grid_y), dim3(kPksThreads), 0, st, in, (int)count, s.cb_pksk, out,
+                       rows_per_out, p.tiles, p.slices);
     HIP_TRY(hipGetLastError());
     return prof.commit();
 }

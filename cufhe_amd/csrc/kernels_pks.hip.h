@@ -7,6 +7,7 @@
 //   3. TRGSW2NTT (bk_to_ntt_kernel, kernels.hip.h) where the caller wants the NTT domain.
 #pragma once
 #include "kernels_lvl2.hip.h"
+#include "launch_plan.h"
 
 namespace cufhe_amd {
 
@@ -61,6 +62,11 @@ constexpr int kPksThreads = 256;
 constexpr int kPksTile = 64;
 constexpr int kPksIBlock = 16;             // input words whose digits are staged per pass
 constexpr int kPksChunks = kCbRowWords / kPksThreads;     // 8
+// The launch shape is plan::plan_private_keyswitch over this geometry.  The kernel cuts i inline, per = ceil(in / slices) without the
+// clamp of plan::pack_slice_begin (its text and code stay as measured: profiles/r28_table_sum_body.md); the two cuts give every slice
+// of every slice count the rule can return the same words
+constexpr plan::PksGeometry kPksGeometry{kPksTile, kPksChunks, kPksIn, kPksIBlock};
+static_assert(plan::slices_match_unclamped_cut(kPksIn, plan::pack_max_slices(kPksGeometry)), "the kernel's cut of i is plan::pack_slice_begin's");
 __global__ __launch_bounds__(kPksThreads) void private_keyswitch_kernel(
     const uint64_t* __restrict__ in, int count, const uint32_t* __restrict__ key, uint32_t* __restrict__ out, int rows_per_out,
     int tiles, int slices)

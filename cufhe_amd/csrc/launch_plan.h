@@ -248,46 +248,55 @@ inline bool lvl2_quarters(size_t count, int cus, const Tuning& t)
     return t.lvl2_kernel < 0 ? count > device_cus(cus) : t.lvl2_kernel == 1;
 }
 
-// Launch shape of private_keyswitch_kernel: tiles of `tile` inputs share every key slice, two times `chunks` workgroups per tile; when
-// the tiles give fewer than four workgroups per CU the i range (`in_words`, staged `i_block` at a time) is cut into slices (partial
-// sums by vector atomics into a zeroed output)
-struct PksGeometry { int tile, chunks, in_words, i_block; };
-struct PksPlan { int tiles, slices; };
-inline PksPlan plan_private_keyswitch(size_t count, int cus, PksGeometry g)
-{
-    const int tiles = (int)((count + g.tile - 1) / g.tile);
-    const long wgs = (long)tiles * 2 * g.chunks;
-    const long want = 4L * (long)device_cus(cus);
-    if (wgs >= want || wgs == 0) return {tiles, 1};
-    return {tiles, (int)std::min<long>((want + wgs - 1) / wgs, (g.in_words + g.i_block - 1) / g.i_block)};
-}
-
-// Launch shape of pack_keyswitch_kernel (kernels_pack.hip.h): `chunks` workgroups per tile of `tile` inputs (one per 256 of the 2N row
-// words); as for the private key switch, tiles that give fewer than four workgroups per CU cut the i range (`in_words`, staged `i_block`
-// at a time) into slices.  Every workgroup adds into the zeroed outputs with vector atomics at any shape, so the words do not depend
-// on it.  grid_x = chunks * tiles (tile = blockIdx.x % tiles), grid_y = slices.
-struct PackGeometry { int tile, chunks, in_words, i_block; };
-struct PackPlan { int tiles, slices; unsigned grid_x, grid_y; };
-constexpr int pack_max_slices(PackGeometry g) { return (g.in_words + g.i_block - 1) / g.i_block; }
+// Launch shape of the tile table-sum kernels (private_keyswitch_kernel, kernels_pks.hip.h, with two key functions; pack_keyswitch_kernel
+// and pack_keyswitch_desc_kernel, kernels_pack.hip.h, with one): tiles of `tile` inputs share every key slice, `chunks` workgroups per tile and key function (one
+// per 256 of the 2N row words); tiles that give fewer than four workgroups per CU cut the i range (`in_words`, staged `i_block` at a
+// time) into slices, whose partial sums meet by vector atomics in a zeroed output, so the words do not depend on the shape.
+// forced_slices > 0 ("pack_slices") sets the slices instead, clamped to 1 .. max.
+// grid_x = key_functions * chunks * tiles (tile = blockIdx.x % tiles), grid_y = slices.
+struct TableSumGeometry { int tile, chunks, in_words, i_block; };
+struct TableSumPlan { int tiles, slices; unsigned grid_x, grid_y; };
+constexpr int pack_max_slices(TableSumGeometry g) { return (g.in_words + g.i_block - 1) / g.i_block; }
 // inputs [first, first + n) of tile `tile`; words [begin, end) of slice `slice` (empty for the last slices when `slices` does not
-// divide the range evenly): the kernel and tests/host/plan_pack_harness.cpp both read the plan through these
+// divide the range evenly): the pack kernels and tests/host/plan_pack_harness.cpp both read the plan through these
 constexpr long pack_tile_first(int tile, int tile_size) { return (long)tile * tile_size; }
 constexpr int pack_tile_inputs(int tile, int tile_size, long count) { return (int)(count - pack_tile_first(tile, tile_size) < tile_size ? count - pack_tile_first(tile, tile_size) : tile_size); }
 constexpr int pack_slice_begin(int slice, int slices, int in_words)
 {
     return (in_words + slices - 1) / slices * slice < in_words ? (in_words + slices - 1) / slices * slice : in_words;
 }
-inline PackPlan plan_pack(size_t count, int cus, PackGeometry g, const Tuning& t)
+// pack_slice_begin against the cut without the clamp -- per = ceil(in_words / slices), [slice per, min(in_words, slice per + per)) -- for
+// every slice of every slice count up to max_slices: the same words, or both empty
+constexpr bool slices_match_unclamped_cut(int in_words, int max_slices)
+{
+    for (int slices = 1; slices <= max_slices; slices++) {
+        const int per = (in_words + slices - 1) / slices;
+        for (int slice = 0; slice < slices; slice++) {
+            const int b0 = slice * per, e0 = b0 + per < in_words ? b0 + per : in_words;
+            const int b1 = pack_slice_begin(slice, slices, in_words), e1 = pack_slice_begin(slice + 1, slices, in_words);
+            if (b0 < e0 ? b0 != b1 || e0 != e1 : b1 < e1) return false;
+        }
+    }
+    return true;
+}
+inline TableSumPlan plan_table_sum(size_t count, int cus, TableSumGeometry g, int key_functions, long forced_slices = -1)
 {
     const int tiles = (int)((count + g.tile - 1) / g.tile), max_slices = pack_max_slices(g);
-    const long wgs = (long)tiles * g.chunks;
+    const long wgs = (long)tiles * key_functions * g.chunks;
     const long want = 4L * (long)device_cus(cus);
     long slices = 1;
-    if (t.pack_slices > 0) slices = t.pack_slices;
+    if (forced_slices > 0) slices = forced_slices;
     else if (wgs > 0 && wgs < want) slices = (want + wgs - 1) / wgs;
     slices = std::max(1L, std::min<long>(slices, max_slices));
     return {tiles, (int)slices, (unsigned)wgs, (unsigned)slices};
 }
+// the rule under its two users' names: the private key switch (two key functions, no option) and TLWE packing (one, "pack_slices")
+using PksGeometry = TableSumGeometry;
+using PksPlan = TableSumPlan;
+using PackGeometry = TableSumGeometry;
+using PackPlan = TableSumPlan;
+inline PksPlan plan_private_keyswitch(size_t count, int cus, PksGeometry g) { return plan_table_sum(count, cus, g, 2); }
+inline PackPlan plan_pack(size_t count, int cus, PackGeometry g, const Tuning& t) { return plan_table_sum(count, cus, g, 1, t.pack_slices); }
 
 // ---- linear layers ----
 

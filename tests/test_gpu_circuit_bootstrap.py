@@ -145,18 +145,25 @@ def _stage2_inputs(count, distinct, seed):
     return base, np.arange(count) % distinct
 
 
-@pytest.mark.parametrize("count", [1, 3, 24, 257, 3 * 4096])
-def test_stage2_words(engine2, random_key, count):
+@pytest.mark.parametrize("count, cus", [pytest.param(c, 0, id=str(c)) for c in (1, 3, 24, 257, 3 * 4096)] +
+                         [pytest.param(c, cus, id=f"{c}-cus{cus}") for c in (64, 65) for cus in (40, 104)])
+def test_stage2_words(engine2, random_key, count, cus):
     """private_keyswitch_batch == the numpy gather-sum mod 2^32.  Large counts repeat a set of distinct inputs (67: not a divisor of
-    the tile of 64), so every output is checked at every tile edge and every split-i shape"""
+    the tile of 64), so every output is checked at every tile edge and every split-i shape.  The key switch has no slice option:
+    one full tile, and one full tile plus a tile of one input, run under "cus_override" 40 and 104, which cut i into 10 / 26 slices
+    for one tile and 5 / 13 for two (plan_table_sum with two key functions)"""
     distinct = min(count, 67)
     base, which = _stage2_inputs(count, distinct, seed=count)
     d2 = _upload(engine2, base[which])
     dout = engine2.api.DeviceBuffer(count * 2 * 2 * N)
-    engine2.api.private_keyswitch_batch(d2, dout, count)
-    got = dout.download().reshape(count, 2, 2, N)
+    engine2.api.set_option("cus_override", cus)
+    try:
+        engine2.api.private_keyswitch_batch(d2, dout, count)
+        got = dout.download().reshape(count, 2, 2, N)
+    finally:
+        engine2.api.set_option("cus_override", 0)
     want = cb.private_keyswitch_batch(random_key, base)
-    assert np.array_equal(got, want[which]), f"private key switch words differ at count {count}"
+    assert np.array_equal(got, want[which]), f"private key switch words differ at count {count}, cus_override {cus}"
 
 
 def test_composition_and_ntt_and_recorded(engine2, keys, random_key):
