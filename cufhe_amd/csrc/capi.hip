@@ -68,6 +68,18 @@ struct PinnedBlock { void* host = nullptr; size_t bytes = 0; hipEvent_t done = n
 // ks_digits: the digit words of the stream's last matrix-product key switch (launch_keyswitch), grow-only like the rest.
 struct Workspace { char* base = nullptr; size_t bytes = 0; char* ks_digits = nullptr; size_t ks_digit_bytes = 0; };
 
+// A dynamic-LDS opt-in (hipFuncSetAttribute) made once per device.  Calls on different streams may come from different threads, and each
+// reads and sets the flag of the kernels it launches: atomic, set behind the attribute calls.  Two threads may both find it unset and both
+// make the calls, which are idempotent; no thread launches before its own calls have returned.
+struct OptInFlag {
+    std::atomic<bool> v{false};
+    OptInFlag() = default;
+    OptInFlag(const OptInFlag& o) : v(o.v.load(std::memory_order_acquire)) {}
+    OptInFlag& operator=(const OptInFlag& o) { v.store(o.v.load(std::memory_order_acquire), std::memory_order_release); return *this; }
+    OptInFlag& operator=(bool b) { v.store(b, std::memory_order_release); return *this; }
+    operator bool() const { return v.load(std::memory_order_acquire); }
+};
+
 struct DeviceState {
     bool ntt_ready = false, keys_ready = false;
     int cus = 0;                         // hipDeviceProp_t::multiProcessorCount (launch-shape rules: one grid round = a workgroup per CU)
@@ -82,14 +94,15 @@ struct DeviceState {
     uint32_t* fault_host = nullptr;
     uint32_t* fault = nullptr;
     bool profiling = false;
-    bool br_lds_opt_in = false, ks_lds_opt_in = false;
+    OptInFlag br_lds_opt_in, ks_lds_opt_in;
     // N = 2048 / 64-bit torus (lvl2.inc.h)
-    bool keys2_ready = false, br2_lds_opt_in = false, ks2_lds_opt_in = false;
+    bool keys2_ready = false;
+    OptInFlag br2_lds_opt_in, ks2_lds_opt_in;
     NttTables* tables2 = nullptr;      // [2]: the two half transforms
     double* bk2_ntt = nullptr;
     Ntt512Tables* tables2q = nullptr;  // [4]: the four quarter transforms (kernels_lvl2q.hip.h)
     double* bk2q_ntt = nullptr;        // the same key in the quarter layout
-    bool br2q_lds_opt_in = false;
+    OptInFlag br2q_lds_opt_in;
     uint32_t* ksk2 = nullptr;
     uint64_t* tvs2 = nullptr;          // [kTvRows2][k2N]: the lvl2 user gates' test vectors (cufhe_amd_lvl2_define_gate) and the library's own row (lvl2.inc.h: ensure_tvs2); CleanUp frees it
     uint32_t* cb_pksk = nullptr;       // circuit bootstrapping: the private key-switching key lvl2 -> lvl1 (cb.inc.h)
@@ -421,7 +434,7 @@ plan::KsPlan plan_keyswitch_of(const DeviceState& s, size_t count, plan::KsRule 
 }
 // keyswitch_kernel<S> over `ksk_padded` ([kn][t][2][row_pad] u32); *opted_in: the instantiation's dynamic-LDS opt-in on this device
 template <class S>
-int launch_keyswitch_shared(DeviceState& s, hipStream_t st, const typename S::Desc* d, size_t count, const uint32_t* ksk_padded, bool* opted_in, const plan::KsPlan& p)
+int launch_keyswitch_shared(DeviceState& s, hipStream_t st, const typename S::Desc* d, size_t count, const uint32_t* ksk_padded, OptInFlag* opted_in, const plan::KsPlan& p)
 {
     if (!*opted_in) {
         HIP_TRY(hipFuncSetAttribute((const void*)keyswitch_kernel<S>, hipFuncAttributeMaxDynamicSharedMemorySize, KsDims<S>::lds_bytes));
@@ -1193,7 +1206,10 @@ int cufhe_amd_cleanup(void)
         if (s.pack_key) { HIP_TRY(hipFree(s.pack_key)); s.pack_key = nullptr; }
         if (s.tables2) HIP_TRY(hipFree(s.tables2));
         if (s.tables2q) HIP_TRY(hipFree(s.tables2q));
-        s.keys2_ready = s.br2_lds_opt_in = s.br2q_lds_opt_in = s.ks2_lds_opt_in = false;
+        s.keys2_ready = false;
+        s.br2_lds_opt_in = false;
+        s.br2q_lds_opt_in = false;
+        s.ks2_lds_opt_in = false;
         s.tables2 = nullptr; s.tables2q = nullptr; s.bk2_ntt = nullptr; s.bk2q_ntt = nullptr; s.ksk2 = nullptr;
         if (s.ntt_ready) { HIP_TRY(hipFree(s.tables)); HIP_TRY(hipFree(s.tables_r4)); HIP_TRY(hipFree(s.tables512)); }
         if (s.fault_host) { (void)hipHostFree(s.fault_host); s.fault_host = nullptr; s.fault = nullptr; }   // the fault, if any, ends with the keys
@@ -1202,7 +1218,8 @@ int cufhe_amd_cleanup(void)
         for (auto& kv : s.workspaces) { (void)hipFree(kv.second.base); (void)hipFree(kv.second.ks_digits); }
         s.workspaces.clear();
         s.ntt_ready = s.keys_ready = false;
-        s.br_lds_opt_in = s.ks_lds_opt_in = false;
+        s.br_lds_opt_in = false;
+        s.ks_lds_opt_in = false;
         s.tables = nullptr; s.tables_r4 = nullptr; s.tables512 = nullptr; s.bk_ntt = nullptr; s.ksk = nullptr;
         s.prof = cufhe_amd_profile{};
     }
@@ -1247,6 +1264,7 @@ int cufhe_amd_stream_destroy(int device, void* stream)
             s.workspaces.erase(it);
         }
     }
+    if (int rc = linear_forget_stream(device, (hipStream_t)stream)) return rc;      // the temporary of cufhe_amd_linear_gate_batch
     {
         std::lock_guard<std::mutex> lk(g_sched_mu);
         if (g_scheduler && device < g_scheduler->gpu_num()) {

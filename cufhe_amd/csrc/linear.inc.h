@@ -20,7 +20,8 @@ struct LinearLayer {
     std::vector<int32_t*> weights;      // per logical device: [row_tiles][cols][kLinearTJ]
     std::vector<uint32_t*> bias;        // per logical device: [row_tiles * kLinearTJ]
 };
-// the fused form's temporary of one (device, stream): grow-only, like the key switch's digit words
+// the fused form's temporary of one (device, stream): grow-only, like the key switch's digit words; released by cufhe_amd_stream_destroy
+// (linear_forget_stream) and by CleanUp
 struct LinearTmp { uint32_t* p = nullptr; size_t words = 0; };
 
 std::mutex g_linear_mu;                 // the table and the pool below
@@ -45,6 +46,20 @@ void linear_drop_all()
     g_linear_count = 0;
     for (auto& kv : g_linear_tmp) release(kv.first.first, kv.second.p);
     g_linear_tmp.clear();
+}
+
+// cufhe_amd_stream_destroy: the stream's pooled temporary goes with its workspace (the device is current).  A later stream may get the
+// same handle: it starts without a block, like any new stream.  The stream is drained first -- at no cost behind the workspace release,
+// which has waited already.
+int linear_forget_stream(int device, hipStream_t st)
+{
+    std::lock_guard<std::mutex> lk(g_linear_mu);
+    auto it = g_linear_tmp.find({device, st});
+    if (it == g_linear_tmp.end()) return 0;
+    HIP_TRY(hipStreamSynchronize(st));
+    (void)hipFree(it->second.p);
+    g_linear_tmp.erase(it);
+    return 0;
 }
 
 // the layer of an id, copied out under the lock (a few words and two small vectors); false: never defined, or dropped by CleanUp

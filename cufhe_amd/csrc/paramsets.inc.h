@@ -9,7 +9,8 @@
 namespace {
 
 struct PsState {
-    bool ready = false, lds_opt_in = false, lds_opt_in_tv = false, ks_lds_opt_in = false;
+    bool ready = false;
+    OptInFlag lds_opt_in, lds_opt_in_tv, ks_lds_opt_in;
     double* bk_ntt = nullptr;
     uint32_t* ksk = nullptr;
     uint32_t* ksk_padded = nullptr;   // sets whose key switch has the default shape: rows padded for keyswitch_kernel
@@ -74,7 +75,7 @@ const typename Poly<PS::Nbit>::Tables* ps_tables_batch(DeviceState& s)
 template <class PS, bool TV>
 int ps_launch_blind_rotate_tv(DeviceState& s, PsState& ps, hipStream_t st, const LinDesc* d, size_t count, int steps, uint32_t* dump)
 {
-    bool& opt_in = TV ? ps.lds_opt_in_tv : ps.lds_opt_in;
+    OptInFlag& opt_in = TV ? ps.lds_opt_in_tv : ps.lds_opt_in;
     if (!opt_in) {
         HIP_TRY(hipFuncSetAttribute((const void*)blind_rotate_ps_kernel<PS, TV>, hipFuncAttributeMaxDynamicSharedMemorySize, PsLds<PS>::bytes));
         HIP_TRY(hipFuncSetAttribute((const void*)blind_rotate_ps_batch_kernel<PS, TV>, hipFuncAttributeMaxDynamicSharedMemorySize, PsbLds<PS>::bytes));

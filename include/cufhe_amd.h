@@ -17,6 +17,18 @@
  *   - "device" is the reference's GPU index in [0, gpuNum) (Stream::device_id(),
  *     include/cufhe_gpu.cuh:152-189).
  *   - "stream" is an opaque hipStream_t (NULL = the device's default stream).
+ *     The stream contract of every cufhe_amd_*_batch / _list entry point (tests/test_gpu_stream_contract.py): a call is asynchronous
+ *     and ordered on its stream -- it may return before any of its work has run, and it runs behind everything issued on that
+ *     stream before it.  HOST argument arrays (ops, exponents, src / idx, dst / pos, the pointer lists) are consumed before the
+ *     call returns: the caller may overwrite or free them at once.  DEVICE operands must stay valid and unmodified until the stream
+ *     has reached the call (outputs: until it has completed it).  Distinct streams are independent: each has its own workspace and
+ *     temporaries in the library, streams of cufhe_amd_stream_create do not order against the NULL stream, and calls on different
+ *     streams may be in flight together.  Calls on different streams may come from different threads, one stream per thread at a
+ *     time; calls on one stream are issued by one thread at a time.  cufhe_amd_set_option and the Initialize / define / CleanUp
+ *     calls are not meant to run beside batch calls of another thread ("br_shape" is the calling thread's own).
+ *     cufhe_amd_stream_destroy completes the stream's work (no synchronise is needed first) and releases everything the library
+ *     pooled for the stream: its workspace, the digit words of its matrix key switches, the temporary of
+ *     cufhe_amd_linear_gate_batch.
  *   - level 0 ciphertexts are lvl0 TLWEs: n+1 = 631 uint32 words (a[0..n-1], b);
  *     level 1 ciphertexts are lvl1 TLWEs: N+1 = 1025 words (TFHEpp::TLWE<P>,
  *     include/cufhe_gpu.cuh:118).  All ciphertext pointers passed to gate functions are

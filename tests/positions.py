@@ -19,6 +19,7 @@ OPTION_DEFAULTS = {
     "ks_wg_threshold": -1, "ks_split_threshold": -1, "ks_per_wg": -1, "ks_slices": -1,
     "ps_batch_threshold": -1, "lvl2_kernel": -1, "lvl0_ring": 1024, "cus_override": 0,
     "param_set": -1, "sched_zero_copy": 1, "sched_rename": 1,
+    "br_shape": 0, "ks_mm_threshold": -1, "cb_rotations": 3,         # "br_shape" is the calling thread's own
 }
 
 
